@@ -1,9 +1,16 @@
 #!/usr/bin/env python3
 """Headline benchmark: min-snap trajectories/sec (10-seg, order-7, 3-axis) at batch = 65k.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
+
+A plain run sets up, warms up, times the K steps, writes what the last of them computed
+if --dump-outputs is given, and prints the headline line.  --full adds everything else
+the benchmark measures or checks (the bit-for-bit re-solve of the timed region's output,
+the one-stream kernel roofline, per-launch statistics, the other methods, sizes and
+configurations, the host and node paths, the CPU baseline and its oracle check); the
+side-line options below select among those and have no effect without it.
 
 One "step" = one solve of one batch of B = 65,536 synthetic trajectories (M = 10)
 per GPU (BASELINE.json configs[2] / SURVEY.md §8(d) config 3), inputs resident in
@@ -825,6 +832,20 @@ class Lane:
     def failures(self) -> int:
         return sum(int((b[3] != 0).sum().item()) for b in self.bufs)
 
+    def timed_failures(self, K: int) -> int:
+        """Non-zero statuses in the sets a timed region of K steps wrote (set k % sets, k < K)."""
+        return sum(int((self.bufs[i][3] != 0).sum().item()) for i in {k % len(self.bufs) for k in range(K)})
+
+    def last_step_outputs(self, K: int, index):
+        """What step K - 1 of a timed region wrote, as its caller receives it: the
+        coefficients [B, M, 3, 8] (here: of the trajectories in `index`) and every
+        trajectory's status, on the host."""
+        import torch
+        _, _, dC, dS = self.bufs[(K - 1) % len(self.bufs)]
+        with torch.cuda.device(self.dev):
+            idx = torch.from_numpy(index).to(self.dev)
+            return dC.index_select(0, idx).cpu().numpy(), dS.cpu().numpy()
+
     def reset_outputs(self):
         """Every set's coefficients to NaN and statuses to -1 (no solve writes -1), so a
         check after a timed region sees only what that region wrote."""
@@ -982,6 +1003,42 @@ def config5_full_line(devs, reps=3, B_total=1048576, iters=10, k_T=1.0, eta=0.1)
             "status_failures": bad, "costs_finite": finite}
 
 
+DUMP_SAMPLE_BYTES = 32 << 20  # coefficients per dump, over every GPU of the run (a dump stays under 64 MB)
+DUMP_SAMPLE_SEED = 20251015
+
+
+def dump_outputs(out_dir: str, lanes, gpu_indices, n_total: int, K: int) -> dict:
+    """--dump-outputs: what the timed region's last step (k = K - 1, batch (K - 1) % sets)
+    computed on each of this process's devices, as <name>.npy under `out_dir`:
+
+      coeffs.npy        float64 [n, M, 3, 8]: the coefficients of a fixed, seeded sample of
+                        n trajectories (all of them if the batch fits DUMP_SAMPLE_BYTES; the
+                        headline batch's 126 MB do not), in ascending trajectory order;
+      status.npy        float64 [B]: every trajectory's status (0 = solved);
+      sample_index.npy  float64 [n]: the sampled trajectories' indices (GPU 0's process only).
+
+    GPU g > 0 of the run writes coeffs_gpu<g>.npy / status_gpu<g>.npy.  The inputs are
+    seeded, so the same arguments give the same inputs, sample and file names in every run."""
+    lane0 = lanes[0]
+    per_traj = lane0.M * 3 * 8 * 8
+    n = int(max(1, min(lane0.B, DUMP_SAMPLE_BYTES // (per_traj * n_total))))
+    index = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(lane0.B, size=n, replace=False)).astype(np.int64)
+    os.makedirs(out_dir, exist_ok=True)
+    files, nbytes = [], 0
+    for L, g in zip(lanes, gpu_indices):
+        C, st = L.last_step_outputs(K, index)
+        arrays = {"coeffs": C.astype(np.float64, copy=False), "status": st.astype(np.float64)}
+        if g == 0:
+            arrays["sample_index"] = index.astype(np.float64)
+        for name, a in arrays.items():
+            fn = name + (f"_gpu{g}" if g and name != "sample_index" else "") + ".npy"
+            np.save(os.path.join(out_dir, fn), a)
+            files.append(fn)
+            nbytes += a.nbytes
+    return {"dir": out_dir, "files": files, "bytes": nbytes, "step": K - 1, "set": (K - 1) % len(lane0.bufs),
+            "trajectories_sampled": n, "trajectories": lane0.B, "sample_seed": DUMP_SAMPLE_SEED}
+
+
 def full_lines_child(n: int, timeout_s: float) -> dict:
     """config4_full / config5_full over devices 0..n-1, run by `bench.py --gpus n
     --full-lines-only` as a child process (started fresh, not forked from this GPU
@@ -1019,6 +1076,13 @@ def main():
                          "control flow with several ranks on one GPU)")
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also run every check and side measurement (verification of the "
+                         "timed region's output, one-stream roofline, per-launch statistics, the side lines "
+                         "selected by the options below, the CPU baseline)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last of them computed as DIR/<name>.npy "
+                         "(see dump_outputs)")
     ap.add_argument("--batch", type=int, default=65536, help="trajectories per GPU")
     ap.add_argument("--segments", type=int, default=10)
     ap.add_argument("--sets", type=int, default=4,
@@ -1171,14 +1235,74 @@ def main():
     el = all_ranks(time.perf_counter() - t0, dist.ReduceOp.MAX if world > 1 else None)
     launch_each = [L.ev0.elapsed_time(L.ev1) / K for L in lanes]
     step_ms_max = all_ranks(max(launch_each), dist.ReduceOp.MAX if world > 1 else None)
+    launch_mode = ("hip_graph_of_K_steps" + (f"_over_{nstreams}_streams" if nstreams > 1 else "")) if graphed \
+        else "python_loop"
+    bpl = algorithmic_bytes_per_traj(M) * B
+    if mode == "ranks":
+        parallelism = f"shard{n_total}: one rank per GPU (independent trajectories, no collective)"
+    else:
+        parallelism = (f"shard{n_total}: one process, one handle + stream + graph per device, launched from one "
+                       f"thread (independent trajectories, no collective)")
+    # the head of the result line: the headline figure and what it was measured on
+    head = {
+        "metric": "min-snap trajectories/sec (10-seg, order-7, 3-axis) at batch=65k; 1/2/4/8 GPU",
+        "value": n_total * B * K / el,
+        "unit": "trajectories/s",
+        "n_gpus": n_total,
+        "steps": K,
+        "warmup": args.warmup,
+        "ms_per_step": el / K * 1e3,
+        "higher_is_better": True,
+        "scaling": "weak",
+        "vs_baseline": None,
+        "dtype": "f64",
+        "data": "synthetic (SURVEY.md 8(d): seed 20251015+GPU index(+7919 i for batch i), room-bound uniform "
+                "waypoints, T=clip(|dw|/1m/s,0.5,10), rest-to-rest)",
+        "config": {"workload": f"config3: {B} trajectories/GPU x {M} segments, order 7, 3 axes, "
+                               f"coefficients [traj][seg][axis][8] fp64 in HBM; a fresh batch every step "
+                               f"({sets} batches rotated, {sets * bpl / 1e6:.0f} MB per GPU), "
+                               f"{nstreams} launch stream(s) per device",
+                   "batch_per_gpu": B, "segments": M, "sets": sets, "method": args.method,
+                   "launch": launch_mode, "streams_per_device": nstreams,
+                   "processes": world, "devices_per_process": len(devs),
+                   "parallelism": parallelism},
+    }
+    if capture_error is not None:
+        head["config"]["graph_capture_error"] = capture_error
+    if args.dump_outputs:
+        gpu_indices = [rank] if mode == "ranks" else devs
+        head["outputs_dumped"] = dump_outputs(args.dump_outputs, lanes, gpu_indices, n_total, K)
+
+    def finish():
+        barrier()
+        for L in lanes:
+            for sv in L.solvers:
+                sv.close()
+        if world > 1:
+            dist.destroy_process_group()
+
+    if not args.full:
+        # a plain run ends here: the statuses the timed steps wrote, and the line
+        bad = all_ranks(float(sum(L.timed_failures(K) for L in lanes)), dist.ReduceOp.SUM if world > 1 else None)
+        assert bad == 0, f"solver reported {int(bad)} failures in the timed steps"
+        if rank == 0:
+            rate = bpl / (step_ms_max * 1e-3) / 1e9
+            head["roofline"] = {"bound": "hbm", "achieved": rate, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                                "frac": rate / HBM_PEAK_GBS, "algorithmic_bytes_per_launch": bpl,
+                                "launch_ms": step_ms_max,
+                                "launch_ms_how": "the headline region's events / K (steps overlap across the "
+                                                 "launch streams); --full times the kernels back to back"}
+            head["full"] = False
+            print(json.dumps(head), flush=True)
+        finish()
+        return
+
     # outside the timed region: what the K steps wrote, against a one-stream re-solve
     checks = [L.verify(K) for L in lanes]
     ver_ok = all(c["status_ok"] and c["bitwise_equal_one_stream_resolve"] for c in checks)
     ver_ok = all_ranks(1.0 if ver_ok else 0.0, dist.ReduceOp.MIN if world > 1 else None) == 1.0
     assert ver_ok, f"the timed region's output failed verification: {checks}"
     timed_set0 = lane0.bufs[0][2][: min(B, 65536)].cpu().numpy().reshape(-1, 3, 8) if rank == 0 else None
-    launch_mode = ("hip_graph_of_K_steps" + (f"_over_{nstreams}_streams" if nstreams > 1 else "")) if graphed \
-        else "python_loop"
     for L in lanes:
         L.graph = None
     # The roofline is the kernel's own rate: with steps overlapping across streams a step's
@@ -1317,38 +1441,12 @@ def main():
         cpu, oracle_check = cpu_baseline(B, M, args.cpu_seconds, check=timed_set0)
 
     if rank == 0:
-        bpl = algorithmic_bytes_per_traj(M) * B
         achieved = bpl / (launch_ms_max * 1e-3) / 1e9
         key = f"B{B}_M{M}_{args.method}_sets{sets}"
         traffic = load_traffic(key)
-        value = n_total * B * K / el
-        if mode == "ranks":
-            parallelism = f"shard{n_total}: one rank per GPU (independent trajectories, no collective)"
-        else:
-            parallelism = (f"shard{n_total}: one process, one handle + stream + graph per device, launched from one "
-                           f"thread (independent trajectories, no collective)")
-        line = {
-            "metric": "min-snap trajectories/sec (10-seg, order-7, 3-axis) at batch=65k; 1/2/4/8 GPU",
-            "value": value,
-            "unit": "trajectories/s",
-            "n_gpus": n_total,
-            "steps": K,
-            "warmup": args.warmup,
-            "ms_per_step": el / K * 1e3,
-            "higher_is_better": True,
-            "scaling": "weak",
-            "vs_baseline": None,
-            "dtype": "f64",
-            "data": "synthetic (SURVEY.md 8(d): seed 20251015+GPU index(+7919 i for batch i), room-bound uniform "
-                    "waypoints, T=clip(|dw|/1m/s,0.5,10), rest-to-rest)",
-            "config": {"workload": f"config3: {B} trajectories/GPU x {M} segments, order 7, 3 axes, "
-                                   f"coefficients [traj][seg][axis][8] fp64 in HBM; a fresh batch every step "
-                                   f"({sets} batches rotated, {sets * bpl / 1e6:.0f} MB per GPU), "
-                                   f"{nstreams} launch stream(s) per device",
-                       "batch_per_gpu": B, "segments": M, "sets": sets, "method": args.method,
-                       "launch": launch_mode, "streams_per_device": nstreams,
-                       "processes": world, "devices_per_process": len(devs),
-                       "parallelism": parallelism},
+        dumped = head.pop("outputs_dumped", None)
+        line = dict(head)
+        line.update({
             "roofline": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
                          "frac": achieved / HBM_PEAK_GBS,
                          "traffic": traffic,
@@ -1403,16 +1501,12 @@ def main():
             "host_path": host,
             "node_config1": node,
             "node_config1_host_backend": node_host,
-        }
-        if capture_error is not None:
-            line["config"]["graph_capture_error"] = capture_error
+        })
+        line["full"] = True
+        if dumped is not None:
+            line["outputs_dumped"] = dumped
         print(json.dumps(line), flush=True)
-    barrier()
-    for L in lanes:
-        for sv in L.solvers:
-            sv.close()
-    if world > 1:
-        dist.destroy_process_group()
+    finish()
 
 
 if __name__ == "__main__":

@@ -73,13 +73,13 @@ for step in "$@"; do
         tail -3 "$log"
         [ $rc -eq 0 ] || end "$step" $rc ;;
     bench)
-        timeout -k 10 300 python bench.py --steps 50 --warmup 5 > "$OUT/bench.json" 2> "$OUT/bench.err" || end "$step" $?
+        timeout -k 10 300 python bench.py --full --steps 50 --warmup 5 > "$OUT/bench.json" 2> "$OUT/bench.err" || end "$step" $?
         cut -c1-400 "$OUT/bench.json" ;;
     prof)
         timeout -k 10 300 rocprofv3 --kernel-trace --stats -d "$OUT/prof" -o run --output-format csv -- \
-            python3 bench.py --steps 50 --warmup 5 --cpu-seconds 0 $SIDE_OFF > "$OUT/prof_bench.json" 2> "$OUT/prof.err" || end "$step" $?
+            python3 bench.py --full --steps 50 --warmup 5 --cpu-seconds 0 $SIDE_OFF > "$OUT/prof_bench.json" 2> "$OUT/prof.err" || end "$step" $?
         timeout -k 10 300 rocprofv3 --kernel-trace --stats -d "$OUT/prof_full" -o run --output-format csv -- \
-            python3 bench.py --steps 20 --warmup 3 --cpu-seconds 0 --dense-steps 2 > "$OUT/prof_full_bench.json" 2> "$OUT/prof_full.err" || end "$step" $?
+            python3 bench.py --full --steps 20 --warmup 3 --cpu-seconds 0 --dense-steps 2 > "$OUT/prof_full_bench.json" 2> "$OUT/prof_full.err" || end "$step" $?
         find "$OUT/prof" "$OUT/prof_full" -name '*stats*' ;;
     pmc)
         bash scripts/gpu_profile.sh || end "$step" $?

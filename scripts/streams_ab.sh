@@ -6,11 +6,11 @@ set -o pipefail
 cd "${GRAFT_REPO_ROOT:-/root/repo}"
 export TMPDIR=/tmp
 O=gpurun_out/${1:-streams}; mkdir -p $O
-SIDE="--dense-steps 0 --band-steps 0 --sample-traj 0 --config5 0 --config4 0 --cache-resident 0 --host-line 0 --node-line 0 --uniform-large-m 0 --config2 0 --cpu-seconds 0"
+SIDE="--full --dense-steps 0 --band-steps 0 --sample-traj 0 --config5 0 --config4 0 --cache-resident 0 --host-line 0 --node-line 0 --uniform-large-m 0 --config2 0 --cpu-seconds 0"
 for s in 4 2 1 4 2 1; do
   timeout -k 10 200 python bench.py --steps 50 --warmup 5 --streams $s $SIDE >> $O/ab_streams.jsonl 2>> $O/ab.err || exit 1
 done
-timeout -k 10 400 python bench.py --steps 50 --warmup 5 > $O/bench.json 2> $O/bench.err || exit 1
+timeout -k 10 400 python bench.py --full --steps 50 --warmup 5 > $O/bench.json 2> $O/bench.err || exit 1
 timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $O/prof -o run --output-format csv -- python3 bench.py --steps 50 --warmup 5 $SIDE > $O/prof_bench.json 2> $O/prof.err || exit 1
 python3 -c "
 import json
