@@ -40,7 +40,9 @@
  *     handle must be replayed in stream order with each other.  Calls that upload a
  *     host-side launch plan or grow scratch at call time (ragged batches,
  *     tgms_refine_loop_device, the multi-GPU calls, a band capture with no slab large
- *     enough) return TGMS_ERR_UNSUPPORTED while their stream is capturing;
+ *     enough) return TGMS_ERR_UNSUPPORTED while their stream is capturing.
+ *     tgms_extrema_batch_device (one kernel, no plan, no scratch) may be captured for any
+ *     batch, ragged included;
  *   - there is no CPU fallback: with no usable GPU, tgms_create fails with
  *     TGMS_ERR_NO_DEVICE.  A GPU-less node asks for the host backend explicitly
  *     (tgms_create_host: solve + sample on the CPU, config 1).
@@ -110,9 +112,10 @@ const char* tgms_status_string(int status);
 tgms_status tgms_create(tgms_handle** out, int device);
 /* The explicit host backend (BASELINE config 1: a ROS 2 node with no GPU; the reference
  * generates on the executor thread's CPU, src/TrajectoryGenerator.cpp:54-57, :71).  A host
- * handle runs tgms_solve_batch (reduced method) and tgms_sample_batch on the calling thread
- * with the GPU path's conventions; every other entry point returns TGMS_ERR_UNSUPPORTED on
- * it.  Chosen by the caller only: tgms_create never falls back to it. */
+ * handle runs tgms_solve_batch (reduced method), tgms_sample_batch and tgms_extrema_batch on
+ * the calling thread with the GPU path's conventions; every other entry point returns
+ * TGMS_ERR_UNSUPPORTED on it.  Chosen by the caller only: tgms_create never falls back to
+ * it. */
 tgms_status tgms_create_host(tgms_handle** out);
 void tgms_destroy(tgms_handle* h);
 /* Last error text of this handle ("" if none).  Valid until the next call. */
@@ -199,6 +202,54 @@ tgms_status tgms_sample_batch_device(tgms_handle* h, int32_t B, const int32_t* d
                                      double dt, int yaw_mode, double yaw_const,
                                      const int64_t* d_sample_offsets, double* d_out,
                                      void* stream);
+
+/* ---- feasibility check at dt: extents, peaks, limit flags ----
+ * The samples above, reduced per trajectory without being written anywhere: over the
+ * tgms_sample_count(sum_i T_i, dt) samples of trajectory b (the sampler's times, segment
+ * scan, prefix sums of T and Horner chains, the last sample pinned to the last waypoint and
+ * the final end derivatives or zeros) one record of TGMS_EXTREMA_STRIDE doubles
+ *     pmin[3] pmax[3] v_peak a_peak j_peak duration
+ * with x_peak = sqrt(max_k (x_x^2 + x_y^2 + x_z^2)) and duration = that prefix sum of T.
+ * This is the sampled-extrema check of the node's trajectoryInsideBounds at resolution dt,
+ * not a continuous root-find: an excursion between two samples is not seen.  The work grows
+ * with sum_i T_i / dt; nothing of it is stored, so a batch whose samples would not fit on
+ * the device can still be checked.
+ *   flags [B] (int32, nullable) receive TGMS_FEAS_* bits against `limits`, a host struct
+ * read at call time (its values travel as kernel arguments).  All comparisons are strict (a
+ * value equal to its limit is inside) and use the very values written to the record.
+ * +-inf entries are unchecked; a NaN entry or pmin > pmax is TGMS_ERR_INVALID_ARG; limits
+ * == NULL checks nothing, so the flags can then carry TGMS_FEAS_NONFINITE only.  A
+ * trajectory with a non-finite coefficient, time, final waypoint, final end derivative or
+ * result (or a negative sum of times, more than 2^53 samples, or, in the device call, a
+ * segment count outside 1..TGMS_MAX_SEGMENTS) gets TGMS_FEAS_NONFINITE and no other bit, and
+ * its record is unspecified (NaNs today); its neighbours are unaffected.  At least one of
+ * extrema / flags must be non-NULL.
+ *   tgms_extrema_batch_device needs no host plan and no handle scratch, so it may be captured
+ * into a HIP graph for any batch, ragged included.  On a multi handle it runs on device 0;
+ * on a host handle it returns TGMS_ERR_UNSUPPORTED, and tgms_extrema_batch runs on the
+ * calling thread. */
+#define TGMS_EXTREMA_STRIDE 10
+#define TGMS_FEAS_BOX 1        /* some sampled position outside [pmin, pmax] */
+#define TGMS_FEAS_SPEED 2      /* v_peak > v_max */
+#define TGMS_FEAS_ACCEL 4      /* a_peak > a_max */
+#define TGMS_FEAS_JERK 8       /* j_peak > j_max */
+#define TGMS_FEAS_NONFINITE 16 /* a coefficient, time or result of this trajectory is not finite */
+typedef struct tgms_limits {
+    double pmin[3], pmax[3], v_max, a_max, j_max;
+} tgms_limits;
+tgms_status tgms_extrema_batch_device(tgms_handle* h, int32_t B, const int32_t* d_seg_offsets,
+                                      const double* d_waypoints, const double* d_seg_times,
+                                      const double* d_end_derivs, const double* d_coeffs, double dt,
+                                      const tgms_limits* limits /* host, nullable */,
+                                      double* d_extrema /* [B][10], nullable */,
+                                      int32_t* d_flags /* [B], nullable */, void* stream);
+/* Host pointers, blocking: one upload, the launch, and one download: records and flags sit
+ * in one workspace region, 80 B + 4 B per trajectory, copied back at once when both are
+ * asked for. */
+tgms_status tgms_extrema_batch(tgms_handle* h, int32_t B, const int32_t* seg_offsets,
+                               const double* waypoints, const double* seg_times, const double* end_derivs,
+                               const double* coeffs, double dt, const tgms_limits* limits,
+                               double* extrema, int32_t* flags);
 
 /* ---- multi-GPU ----
  * One process drives devices 0 .. device_count-1 through one handle that owns one RCCL

@@ -18,6 +18,8 @@ ABI_VERSION = 2
 MAX_SEGMENTS = 16
 DENSE_MAX_SEGMENTS = 10
 GOAL_STRIDE = 14
+EXTREMA_STRIDE = 10  # pmin[3] pmax[3] v_peak a_peak j_peak duration
+FEAS_BOX, FEAS_SPEED, FEAS_ACCEL, FEAS_JERK, FEAS_NONFINITE = 1, 2, 4, 8, 16
 
 # Every symbol include/tgms.h declares (checked by tests/test_capi_symbols.py).
 EXPORTS = [
@@ -27,6 +29,7 @@ EXPORTS = [
     "tgms_refine_uniform_device", "tgms_refine_batch_device", "tgms_refine_loop_device", "tgms_refine_batch",
     "tgms_create_multi", "tgms_device_count", "tgms_plan_shards", "tgms_solve_batch_multi",
     "tgms_solve_batch_multi_device", "tgms_refine_loop_multi_device", "tgms_multi_schedule",
+    "tgms_extrema_batch", "tgms_extrema_batch_device",
 ]
 
 SCHED_REFINE, SCHED_END_DERIVS, SCHED_COEFFS, SCHED_STATUS, SCHED_COST, SCHED_SELF_GATHER = 1, 2, 4, 8, 16, 32
@@ -43,6 +46,20 @@ class Xfer(ctypes.Structure):
     _fields_ = [("dev", ctypes.c_int32), ("piece", ctypes.c_int32), ("gather", ctypes.c_int32),
                 ("array", ctypes.c_int32), ("batch_elem", ctypes.c_int64), ("ws_byte", ctypes.c_int64),
                 ("count", ctypes.c_int64), ("elem_bytes", ctypes.c_int32), ("group", ctypes.c_int32)]
+
+
+class Limits(ctypes.Structure):
+    """tgms_limits (include/tgms.h): the box and the speed / acceleration / jerk limits of a
+    feasibility check.  The default checks nothing (+-inf everywhere)."""
+    _fields_ = [("pmin", ctypes.c_double * 3), ("pmax", ctypes.c_double * 3), ("v_max", ctypes.c_double),
+                ("a_max", ctypes.c_double), ("j_max", ctypes.c_double)]
+
+    def __init__(self, pmin=None, pmax=None, v_max=float("inf"), a_max=float("inf"), j_max=float("inf")):
+        super().__init__()
+        self.pmin[:] = [float(x) for x in (pmin if pmin is not None else [float("-inf")] * 3)]
+        self.pmax[:] = [float(x) for x in (pmax if pmax is not None else [float("inf")] * 3)]
+        self.v_max, self.a_max, self.j_max = float(v_max), float(a_max), float(j_max)
+
 
 _lib = None
 
@@ -120,6 +137,10 @@ def load(path: str = ""):
     L.tgms_refine_loop_multi_device.restype = ctypes.c_int
     L.tgms_multi_schedule.argtypes = [i32, i32, vp, ctypes.c_int, i32, vp, vp, vp, i32, vp, vp, i32, vp]
     L.tgms_multi_schedule.restype = ctypes.c_int
+    L.tgms_extrema_batch_device.argtypes = [vp, i32, vp, vp, vp, vp, vp, dbl, ctypes.POINTER(Limits), vp, vp, vp]
+    L.tgms_extrema_batch_device.restype = ctypes.c_int
+    L.tgms_extrema_batch.argtypes = [vp, i32, vp, vp, vp, vp, vp, dbl, ctypes.POINTER(Limits), vp, vp]
+    L.tgms_extrema_batch.restype = ctypes.c_int
     if L.tgms_abi_version() != ABI_VERSION:
         raise ImportError(f"libtgms ABI {L.tgms_abi_version()} != {ABI_VERSION}")
     _lib = L

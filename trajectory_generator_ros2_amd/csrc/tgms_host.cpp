@@ -88,6 +88,24 @@ void hermite(double w0, double w1, const double (&s)[3], const double (&e)[3], d
     c[7] = P7 * r4;
 }
 
+// p, v, a, j of one segment (c [3][8]) at local time lt into o[q*3 + axis]: d^q/dt^q by
+// Horner on j!/(j-q)! c_j, the GPU sampler's four FMA chains.
+void pvaj(const double* c3, double lt, double* o) {
+    for (int a = 0; a < 3; ++a) {
+        const double* c = c3 + a * 8;
+        for (int q = 0; q < 4; ++q) {
+            auto coef = [&](int j) {
+                double f = 1.0;
+                for (int m = 0; m < q; ++m) f *= (double)(j - m);
+                return f * c[j];
+            };
+            double s = coef(7);
+            for (int j = 6; j >= q; --j) s = std::fma(s, lt, coef(j));
+            o[q * 3 + a] = s;
+        }
+    }
+}
+
 }  // namespace
 
 int solve(int M, const double* W, const double* T, const double* ED, double* C) {
@@ -204,20 +222,7 @@ void sample(int M, const double* C, const double* T, const double* W, const doub
                 t_cur = t_next;
                 t_next = tau[i + 1 < M ? i + 1 : M];
             }
-            const double lt = t - t_cur;
-            for (int a = 0; a < 3; ++a) {
-                const double* c = C + (i * 3 + a) * 8;
-                for (int q = 0; q < 4; ++q) {  // d^q/dt^q by Horner on j!/(j-q)! c_j
-                    auto coef = [&](int j) {
-                        double f = 1.0;
-                        for (int m = 0; m < q; ++m) f *= (double)(j - m);
-                        return f * c[j];
-                    };
-                    double s = coef(7);
-                    for (int j = 6; j >= q; --j) s = std::fma(s, lt, coef(j));
-                    o[q * 3 + a] = s;
-                }
-            }
+            pvaj(C + i * 24, t - t_cur, o);
         } else {  // the last sample, pinned to the final waypoint and end derivatives
             for (int a = 0; a < 3; ++a) {
                 o[a] = W[M * 3 + a];
@@ -232,6 +237,68 @@ void sample(int M, const double* C, const double* T, const double* W, const doub
         o[12] = yv ? std::atan2(vy, vx) : yaw_const;
         o[13] = yv ? (vx * ay - vy * ax) / s2 : 0.0;
     }
+}
+
+int extrema(int M, const double* C, const double* T, const double* W, const double* ED, double dt,
+            const tgms_limits* lim, double* rec) {
+    double tau[TGMS_MAX_SEGMENTS + 1];
+    tau[0] = 0.0;
+    double acc = 0.0, chk = 0.0;  // chk: 0 while everything read is finite
+    for (int i = 0; i < M; ++i) tau[i + 1] = (acc += T[i]);  // the same order as tgms_sample_offsets
+    for (int q = 0; q < M * 24; ++q) chk += C[q] * 0.0;
+    for (int a = 0; a < 3; ++a) chk += W[M * 3 + a] * 0.0;
+    for (int q = 9; ED && q < 18; ++q) chk += ED[q] * 0.0;
+    const int64_t ns = tgms_sample_count(acc, dt);  // 0: the sum is negative or not finite
+    double lo[3], hi[3], n2[3] = {0.0, 0.0, 0.0};
+    for (int a = 0; a < 3; ++a) lo[a] = HUGE_VAL, hi[a] = -HUGE_VAL;
+    bool bad = !finite(chk) || ns < 2 || !(std::ceil(acc / dt - 1e-9) < 9007199254740992.0);
+    int i = 0;
+    double t_cur = 0.0, t_next = M > 1 ? tau[1] : 0.0;
+    for (int64_t k = 0; !bad && k < ns; ++k) {
+        double o[12];
+        if (k < ns - 1) {
+            const double t = (double)k * dt;
+            while (i + 1 < M && t_next <= t) {  // segment scan, as sample()'s
+                ++i;
+                t_cur = t_next;
+                t_next = tau[i + 1 < M ? i + 1 : M];
+            }
+            pvaj(C + i * 24, t - t_cur, o);
+        } else {  // the pinned last sample
+            for (int a = 0; a < 3; ++a) {
+                o[a] = W[M * 3 + a];
+                for (int q = 1; q < 4; ++q) o[q * 3 + a] = ED ? ED[9 + (q - 1) * 3 + a] : 0.0;
+            }
+        }
+        for (int a = 0; a < 3; ++a) {
+            lo[a] = std::fmin(lo[a], o[a]);
+            hi[a] = std::fmax(hi[a], o[a]);
+        }
+        for (int q = 0; q < 3; ++q) {
+            const double* d = o + 3 + q * 3;
+            n2[q] = std::fmax(n2[q], d[0] * d[0] + d[1] * d[1] + d[2] * d[2]);
+        }
+    }
+    for (int a = 0; a < 3; ++a) {
+        rec[a] = lo[a];
+        rec[3 + a] = hi[a];
+        rec[6 + a] = std::sqrt(n2[a]);
+    }
+    rec[9] = acc;
+    for (int q = 0; q < TGMS_EXTREMA_STRIDE; ++q) bad = bad || !finite(rec[q]);
+    if (bad) {
+        for (int q = 0; q < TGMS_EXTREMA_STRIDE; ++q) rec[q] = NAN;
+        return TGMS_FEAS_NONFINITE;
+    }
+    int fl = 0;
+    if (lim) {  // strict comparisons on the stored values
+        for (int a = 0; a < 3; ++a)
+            if (rec[a] < lim->pmin[a] || rec[3 + a] > lim->pmax[a]) fl |= TGMS_FEAS_BOX;
+        if (rec[6] > lim->v_max) fl |= TGMS_FEAS_SPEED;
+        if (rec[7] > lim->a_max) fl |= TGMS_FEAS_ACCEL;
+        if (rec[8] > lim->j_max) fl |= TGMS_FEAS_JERK;
+    }
+    return fl;
 }
 
 }  // namespace host

@@ -17,5 +17,12 @@ int solve(int M, const double* waypoints, const double* seg_times, const double*
 void sample(int M, const double* coeffs, const double* seg_times, const double* waypoints, const double* end_derivs,
             double dt, int yaw_mode, double yaw_const, int64_t ns, double* out);
 
+// Those ns samples reduced to rec [TGMS_EXTREMA_STRIDE] (pmin pmax v_peak a_peak j_peak
+// duration) without storing them: the same scan and Horner chains as sample().  Returns the
+// TGMS_FEAS_* bits against lim (nullable: nothing checked), TGMS_FEAS_NONFINITE alone (rec
+// all NaN) when an input or a result is not finite.
+int extrema(int M, const double* coeffs, const double* seg_times, const double* waypoints, const double* end_derivs,
+            double dt, const tgms_limits* lim, double* rec);
+
 }  // namespace host
 }  // namespace tgms

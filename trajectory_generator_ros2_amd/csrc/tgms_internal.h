@@ -4,6 +4,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "tgms.h"
+
 namespace tgms {
 
 // Largest M solved at two wavefronts per SIMD (the axis-sequential state of larger M
@@ -125,5 +127,11 @@ hipError_t launch_sample(int32_t B, const int32_t* seg_offsets, const double* W,
                          const double* ED, const double* C, double dt, int yaw_mode,
                          double yaw_const, const int64_t* sample_offsets, double* out,
                          hipStream_t stream);
+
+// Feasibility check: the sampler's samples reduced per trajectory to ext [B][TGMS_EXTREMA_STRIDE]
+// and flags [B] (either nullable), one wavefront per trajectory, nothing per sample stored.
+hipError_t launch_extrema(int32_t B, const int32_t* seg_offsets, const double* W, const double* T,
+                          const double* ED, const double* C, double dt, const tgms_limits& lim, double* ext,
+                          int32_t* flags, hipStream_t stream);
 
 }  // namespace tgms

@@ -136,6 +136,25 @@ class Solver:
             raise TgmsError(st, self.last_error())
         return offs, out
 
+    def extrema(self, seg_offsets, waypoints, seg_times, end_derivs, coeffs, dt: float,
+                limits: Optional[_lib.Limits] = None) -> Tuple[np.ndarray, np.ndarray]:
+        """Feasibility check at dt (include/tgms.h tgms_extrema_batch): (extrema [B,10] =
+        pmin pmax v_peak a_peak j_peak duration, flags [B] of FEAS_* bits against `limits`;
+        None checks nothing, so only FEAS_NONFINITE can appear)."""
+        so = np.ascontiguousarray(seg_offsets, dtype=np.int32)
+        W = np.ascontiguousarray(waypoints, dtype=np.float64).reshape(-1, 3)
+        T = np.ascontiguousarray(seg_times, dtype=np.float64).reshape(-1)
+        ED = None if end_derivs is None else np.ascontiguousarray(end_derivs, dtype=np.float64).reshape(-1, 18)
+        C = np.ascontiguousarray(coeffs, dtype=np.float64)
+        B = so.shape[0] - 1
+        ext = np.zeros((B, _lib.EXTREMA_STRIDE), dtype=np.float64)
+        flags = np.zeros(B, dtype=np.int32)
+        st = self._L.tgms_extrema_batch(self._h, B, _ptr(so), _ptr(W), _ptr(T), _ptr(ED), _ptr(C), float(dt),
+                                        None if limits is None else ctypes.byref(limits), _ptr(ext), _ptr(flags))
+        if st != _lib.OK:
+            raise TgmsError(st, self.last_error())
+        return ext, flags
+
     def refine(self, seg_offsets, waypoints, seg_times, end_derivs=None, k_T: float = 1.0, eta: float = 0.1,
                iters: int = 10, coeffs: bool = True):
         """Time-allocation refinement on the GPU (include/tgms.h tgms_refine_batch).
@@ -229,6 +248,18 @@ class Solver:
                                               _ptr(d_seg_times), _ptr(d_end_derivs), _ptr(d_coeffs), float(dt),
                                               int(yaw_mode), float(yaw_const), _ptr(d_sample_offsets),
                                               _ptr(d_out), ctypes.c_void_p(stream))
+        if st != _lib.OK:
+            raise TgmsError(st, self.last_error())
+
+    def extrema_device(self, B: int, d_seg_offsets, d_waypoints, d_seg_times, d_coeffs, dt: float,
+                       limits: Optional[_lib.Limits] = None, d_extrema=None, d_flags=None, d_end_derivs=None,
+                       stream: int = 0) -> None:
+        """tgms_extrema_batch_device: d_extrema [B,10] fp64 and / or d_flags [B] int32 (at
+        least one); `limits` is read now, so it may change before the kernel runs."""
+        st = self._L.tgms_extrema_batch_device(self._h, int(B), _ptr(d_seg_offsets), _ptr(d_waypoints),
+                                               _ptr(d_seg_times), _ptr(d_end_derivs), _ptr(d_coeffs), float(dt),
+                                               None if limits is None else ctypes.byref(limits),
+                                               _ptr(d_extrema), _ptr(d_flags), ctypes.c_void_p(stream))
         if st != _lib.OK:
             raise TgmsError(st, self.last_error())
 
