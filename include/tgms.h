@@ -41,8 +41,8 @@
  *     host-side launch plan or grow scratch at call time (ragged batches,
  *     tgms_refine_loop_device, the multi-GPU calls, a band capture with no slab large
  *     enough) return TGMS_ERR_UNSUPPORTED while their stream is capturing.
- *     tgms_extrema_batch_device (one kernel, no plan, no scratch) may be captured for any
- *     batch, ragged included;
+ *     tgms_extrema_batch_device and tgms_bounds_batch_device (one kernel, no plan, no
+ *     scratch) may be captured for any batch, ragged included;
  *   - there is no CPU fallback: with no usable GPU, tgms_create fails with
  *     TGMS_ERR_NO_DEVICE.  A GPU-less node asks for the host backend explicitly
  *     (tgms_create_host: solve + sample on the CPU, config 1).
@@ -112,8 +112,8 @@ const char* tgms_status_string(int status);
 tgms_status tgms_create(tgms_handle** out, int device);
 /* The explicit host backend (BASELINE config 1: a ROS 2 node with no GPU; the reference
  * generates on the executor thread's CPU, src/TrajectoryGenerator.cpp:54-57, :71).  A host
- * handle runs tgms_solve_batch (reduced method), tgms_sample_batch and tgms_extrema_batch on
- * the calling thread with the GPU path's conventions; every other entry point returns
+ * handle runs tgms_solve_batch (reduced method), tgms_sample_batch, tgms_extrema_batch and
+ * tgms_bounds_batch on the calling thread with the GPU path's conventions; every other entry point returns
  * TGMS_ERR_UNSUPPORTED on it.  Chosen by the caller only: tgms_create never falls back to
  * it. */
 tgms_status tgms_create_host(tgms_handle** out);
@@ -250,6 +250,47 @@ tgms_status tgms_extrema_batch(tgms_handle* h, int32_t B, const int32_t* seg_off
                                const double* waypoints, const double* seg_times, const double* end_derivs,
                                const double* coeffs, double dt, const tgms_limits* limits,
                                double* extrema, int32_t* flags);
+
+/* ---- continuous feasibility bounds: the same record and flags, no dt ----
+ * The polynomial on the closed interval [0, T_i] of every segment is the whole input: no dt,
+ * no waypoints, no end derivatives.  The record is the TGMS_EXTREMA_STRIDE layout above, so a
+ * consumer of the sampled record can switch calls:
+ *     pmin / pmax   per-axis minimum and maximum of p(t) over all segments' closed intervals
+ *     x_peak        sqrt(max_t (x_x^2 + x_y^2 + x_z^2)) for x = p', p'', p''' over the same set
+ *     duration      the left-to-right prefix sum of T, bit-equal to tgms_extrema_batch's
+ * The quantities are piecewise polynomials of degree <= 7 (the squared norms <= 12), so their
+ * extrema are the values at the segment ends and at the stationary points, which are located
+ * by bisection on the monotone pieces of the derivative: O(M) work per trajectory, independent
+ * of the durations, and no resolution to choose.
+ *   Accuracy: extents within 1e-9 * max|p| of the true continuous extremum, peaks within 1e-9
+ * relative of it.  These are fp64 evaluations at located stationary points, not an
+ * interval-arithmetic certificate.  A stationary point where the derivative touches zero
+ * without a sign change (an inflection, or a minimum / maximum pair closer than the root
+ * resolution) may be skipped; that moves the result by far less than the tolerance.  A
+ * constant trajectory (all coefficients of degree >= 1 zero) gives peaks of exactly 0.0 and
+ * extents that are exactly the point.
+ *   flags: the TGMS_FEAS_* bits against the same tgms_limits, as above: strict comparisons on
+ * the very values stored, +-inf entries unchecked, limits == NULL can yield
+ * TGMS_FEAS_NONFINITE only, a NaN entry or pmin > pmax is TGMS_ERR_INVALID_ARG.  A trajectory
+ * with a non-finite coefficient, time or result, with a T_i that is not > 0 (the solvers
+ * never emit one) or, in the device call, with a segment count outside
+ * 1..TGMS_MAX_SEGMENTS (nothing is read for it) gets TGMS_FEAS_NONFINITE alone and an all-NaN
+ * record; its neighbours are unaffected.  At least one of extrema / flags must be non-NULL;
+ * fp64 device arrays are 16-byte aligned; B == 0 is TGMS_OK and launches nothing.
+ *   tgms_bounds_batch_device is one kernel launch with no host plan and no handle scratch, so
+ * it may be captured into a HIP graph for any batch, ragged included.  On a multi handle it
+ * runs on device 0; on a host handle it returns TGMS_ERR_UNSUPPORTED.  tgms_bounds_batch on a
+ * host handle computes on the calling thread (the same algorithm; host and device agree to
+ * the accuracy above, not to the bit); on a GPU handle it does one upload, the launch and one
+ * download, like tgms_extrema_batch. */
+tgms_status tgms_bounds_batch_device(tgms_handle* h, int32_t B, const int32_t* d_seg_offsets,
+                                     const double* d_seg_times, const double* d_coeffs,
+                                     const tgms_limits* limits /* host, nullable */,
+                                     double* d_extrema /* [B][TGMS_EXTREMA_STRIDE], nullable */,
+                                     int32_t* d_flags /* [B], nullable */, void* stream);
+tgms_status tgms_bounds_batch(tgms_handle* h, int32_t B, const int32_t* seg_offsets,
+                              const double* seg_times, const double* coeffs,
+                              const tgms_limits* limits, double* extrema, int32_t* flags);
 
 /* ---- multi-GPU ----
  * One process drives devices 0 .. device_count-1 through one handle that owns one RCCL

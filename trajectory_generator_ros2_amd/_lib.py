@@ -29,7 +29,7 @@ EXPORTS = [
     "tgms_refine_uniform_device", "tgms_refine_batch_device", "tgms_refine_loop_device", "tgms_refine_batch",
     "tgms_create_multi", "tgms_device_count", "tgms_plan_shards", "tgms_solve_batch_multi",
     "tgms_solve_batch_multi_device", "tgms_refine_loop_multi_device", "tgms_multi_schedule",
-    "tgms_extrema_batch", "tgms_extrema_batch_device",
+    "tgms_extrema_batch", "tgms_extrema_batch_device", "tgms_bounds_batch", "tgms_bounds_batch_device",
 ]
 
 SCHED_REFINE, SCHED_END_DERIVS, SCHED_COEFFS, SCHED_STATUS, SCHED_COST, SCHED_SELF_GATHER = 1, 2, 4, 8, 16, 32
@@ -141,6 +141,10 @@ def load(path: str = ""):
     L.tgms_extrema_batch_device.restype = ctypes.c_int
     L.tgms_extrema_batch.argtypes = [vp, i32, vp, vp, vp, vp, vp, dbl, ctypes.POINTER(Limits), vp, vp]
     L.tgms_extrema_batch.restype = ctypes.c_int
+    L.tgms_bounds_batch_device.argtypes = [vp, i32, vp, vp, vp, ctypes.POINTER(Limits), vp, vp, vp]
+    L.tgms_bounds_batch_device.restype = ctypes.c_int
+    L.tgms_bounds_batch.argtypes = [vp, i32, vp, vp, vp, ctypes.POINTER(Limits), vp, vp]
+    L.tgms_bounds_batch.restype = ctypes.c_int
     if L.tgms_abi_version() != ABI_VERSION:
         raise ImportError(f"libtgms ABI {L.tgms_abi_version()} != {ABI_VERSION}")
     _lib = L

@@ -1919,6 +1919,84 @@ tgms_status tgms_extrema_batch(tgms_handle* h, int32_t B, const int32_t* so, con
     return TGMS_OK;
 }
 
+// ---- continuous feasibility bounds: the same record and flags, no dt ----
+
+tgms_status tgms_bounds_batch_device(tgms_handle* h, int32_t B, const int32_t* d_so, const double* dT,
+                                     const double* dC, const tgms_limits* limits, double* d_extrema,
+                                     int32_t* d_flags, void* stream) {
+    if (!h) return TGMS_ERR_INVALID_ARG;
+    if (h->host) return set_err(h, TGMS_ERR_UNSUPPORTED, "tgms_bounds_batch_device needs a GPU handle (tgms_create)");
+    h->last_error.clear();
+    if (B < 0) return set_err(h, TGMS_ERR_INVALID_ARG, "bad B");
+    tgms_limits lim;
+    if (!resolve_limits(limits, &lim)) return set_err(h, TGMS_ERR_INVALID_ARG, "NaN limit or pmin > pmax");
+    if (!d_extrema && !d_flags) return set_err(h, TGMS_ERR_INVALID_ARG, "d_extrema and d_flags both NULL");
+    if (B == 0) return TGMS_OK;
+    if (!d_so || !dT || !dC) return set_err(h, TGMS_ERR_INVALID_ARG, "NULL device pointer");
+    TGMS_CHECK_ALIGNED(h, dT, dC, d_extrema);
+    TGMS_HIP(h, tgms::launch_bounds(B, d_so, dT, dC, lim, d_extrema, d_flags, static_cast<hipStream_t>(stream)));
+    return TGMS_OK;
+}
+
+tgms_status tgms_bounds_batch(tgms_handle* h, int32_t B, const int32_t* so, const double* seg_times,
+                              const double* coeffs, const tgms_limits* limits, double* extrema, int32_t* flags) {
+    if (!h) return TGMS_ERR_INVALID_ARG;
+    h->last_error.clear();
+    tgms_status s = check_offsets(h, B, so, TGMS_MAX_SEGMENTS, nullptr, nullptr);
+    if (s != TGMS_OK) return s;
+    tgms_limits lim;
+    if (!resolve_limits(limits, &lim)) return set_err(h, TGMS_ERR_INVALID_ARG, "NaN limit or pmin > pmax");
+    if (!extrema && !flags) return set_err(h, TGMS_ERR_INVALID_ARG, "extrema and flags both NULL");
+    if (B == 0) return TGMS_OK;
+    if (!seg_times || !coeffs) return set_err(h, TGMS_ERR_INVALID_ARG, "NULL pointer");
+    if (h->host) {
+        for (int32_t b = 0; b < B; ++b) {
+            const int64_t s0 = so[b];
+            double rec[TGMS_EXTREMA_STRIDE];
+            const int fl = tgms::host::bounds(so[b + 1] - so[b], coeffs + s0 * 24, seg_times + s0, &lim, rec);
+            if (extrema) std::copy(rec, rec + TGMS_EXTREMA_STRIDE, extrema + (int64_t)b * TGMS_EXTREMA_STRIDE);
+            if (flags) flags[b] = fl;
+        }
+        return TGMS_OK;
+    }
+    TGMS_HIP(h, hipSetDevice(h->device));
+    const size_t S = (size_t)so[B];
+    const size_t nT = S, nC = S * 24;
+    size_t off = 0;
+    const size_t oT = off; off = align256(off + nT * 8);
+    const size_t oC = off; off = align256(off + nC * 8);
+    const size_t oSo = off; off = align256(off + (size_t)(B + 1) * 4);
+    // both results in one region, the flags right behind the records: one download
+    const size_t nExt = (size_t)B * TGMS_EXTREMA_STRIDE * 8, nFl = (size_t)B * 4;
+    const size_t oExt = off; off = align256(off + nExt + nFl);
+    const size_t oFl = oExt + nExt;
+    s = ensure_ws(h, off);
+    if (s != TGMS_OK) return s;
+    char* base = static_cast<char*>(h->d_ws);
+    double* dT = reinterpret_cast<double*>(base + oT);
+    double* dC = reinterpret_cast<double*>(base + oC);
+    int32_t* dSo = reinterpret_cast<int32_t*>(base + oSo);
+    double* dExt = extrema ? reinterpret_cast<double*>(base + oExt) : nullptr;
+    int32_t* dFl = flags ? reinterpret_cast<int32_t*>(base + oFl) : nullptr;
+    hipStream_t st = h->stream;
+    TGMS_HIP(h, hipMemcpyAsync(dT, seg_times, nT * 8, hipMemcpyHostToDevice, st));
+    TGMS_HIP(h, hipMemcpyAsync(dC, coeffs, nC * 8, hipMemcpyHostToDevice, st));
+    TGMS_HIP(h, hipMemcpyAsync(dSo, so, (size_t)(B + 1) * 4, hipMemcpyHostToDevice, st));
+    TGMS_HIP(h, tgms::launch_bounds(B, dSo, dT, dC, lim, dExt, dFl, st));
+    if (dExt && dFl) {  // 80 B + 4 B per trajectory in one copy, split on the host
+        std::vector<char> res(nExt + nFl);
+        TGMS_HIP(h, hipMemcpyAsync(res.data(), base + oExt, nExt + nFl, hipMemcpyDeviceToHost, st));
+        TGMS_HIP(h, hipStreamSynchronize(st));
+        std::memcpy(extrema, res.data(), nExt);
+        std::memcpy(flags, res.data() + nExt, nFl);
+        return TGMS_OK;
+    }
+    if (dExt) TGMS_HIP(h, hipMemcpyAsync(extrema, dExt, nExt, hipMemcpyDeviceToHost, st));
+    if (dFl) TGMS_HIP(h, hipMemcpyAsync(flags, dFl, nFl, hipMemcpyDeviceToHost, st));
+    TGMS_HIP(h, hipStreamSynchronize(st));
+    return TGMS_OK;
+}
+
 // ---- multi-GPU ----
 
 tgms_status tgms_create_multi(tgms_handle** out, int device_count) {

@@ -23,6 +23,8 @@
 #include <cfloat>
 #include <cmath>
 
+#include "tgms_bounds_core.h"
+
 namespace tgms {
 namespace host {
 namespace {
@@ -298,6 +300,37 @@ int extrema(int M, const double* C, const double* T, const double* W, const doub
         if (rec[7] > lim->a_max) fl |= TGMS_FEAS_ACCEL;
         if (rec[8] > lim->j_max) fl |= TGMS_FEAS_JERK;
     }
+    return fl;
+}
+
+int bounds(int M, const double* C, const double* T, const tgms_limits* lim, double* rec) {
+    const double inf = HUGE_VAL;
+    const tgms_limits none{{-inf, -inf, -inf}, {inf, inf, inf}, inf, inf, inf};
+    double lo[3], hi[3], n2[3] = {0.0, 0.0, 0.0}, acc = 0.0, chk = 0.0;
+    for (int a = 0; a < 3; ++a) lo[a] = inf, hi[a] = -inf;
+    bool bad = false;
+    for (int i = 0; i < M; ++i) {
+        acc += T[i];  // the same order as tgms_sample_offsets
+        chk += T[i] * 0.0;
+        bad = bad || !(T[i] > 0.0);
+    }
+    for (int q = 0; q < M * 24; ++q) chk += C[q] * 0.0;
+    bad = bad || !finite(chk);
+    for (int i = 0; !bad && i < M; ++i) {  // tgms_bounds_core.h: the kernel's items, one after the other
+        const double* c = C + i * 24;
+        for (int a = 0; a < 3; ++a) {
+            double l, h;
+            tgms::bounds::position_item(c + a * 8, T[i], l, h);
+            lo[a] = std::fmin(lo[a], l);
+            hi[a] = std::fmax(hi[a], h);
+        }
+        n2[0] = std::fmax(n2[0], tgms::bounds::norm_item<1>(c, T[i]));
+        n2[1] = std::fmax(n2[1], tgms::bounds::norm_item<2>(c, T[i]));
+        n2[2] = std::fmax(n2[2], tgms::bounds::norm_item<3>(c, T[i]));
+    }
+    double r[TGMS_EXTREMA_STRIDE];
+    const int fl = tgms::bounds::finish(lo, hi, n2, acc, bad, lim ? *lim : none, r);
+    for (int q = 0; q < TGMS_EXTREMA_STRIDE; ++q) rec[q] = r[q];
     return fl;
 }
 

@@ -24,5 +24,10 @@ void sample(int M, const double* coeffs, const double* seg_times, const double* 
 int extrema(int M, const double* coeffs, const double* seg_times, const double* waypoints, const double* end_derivs,
             double dt, const tgms_limits* lim, double* rec);
 
+// The continuous counterpart (include/tgms.h tgms_bounds_batch): the same record and flags from
+// the stationary points of the polynomials on every segment's closed interval, no dt.  The
+// algorithm is the kernel's (tgms_bounds_core.h), one item after the other.
+int bounds(int M, const double* coeffs, const double* seg_times, const tgms_limits* lim, double* rec);
+
 }  // namespace host
 }  // namespace tgms

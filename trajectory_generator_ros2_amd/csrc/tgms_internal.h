@@ -134,4 +134,8 @@ hipError_t launch_extrema(int32_t B, const int32_t* seg_offsets, const double* W
                           const double* ED, const double* C, double dt, const tgms_limits& lim, double* ext,
                           int32_t* flags, hipStream_t stream);
 
+// Continuous feasibility bounds (tgms_bounds.hip): the same record and flags from the
+// polynomials' stationary points, no dt; a wavefront per tile of 4 trajectories, one launch.
+hipError_t launch_bounds(int32_t B, const int32_t* seg_offsets, const double* T, const double* C,
+                         const tgms_limits& lim, double* ext, int32_t* flags, hipStream_t stream);
 }  // namespace tgms

@@ -155,6 +155,23 @@ class Solver:
             raise TgmsError(st, self.last_error())
         return ext, flags
 
+    def bounds(self, seg_offsets, seg_times, coeffs,
+               limits: Optional[_lib.Limits] = None) -> Tuple[np.ndarray, np.ndarray]:
+        """Continuous feasibility bounds (include/tgms.h tgms_bounds_batch): the record and
+        flags of extrema(), from the polynomials' stationary points on every segment's closed
+        interval instead of samples at a dt."""
+        so = np.ascontiguousarray(seg_offsets, dtype=np.int32)
+        T = np.ascontiguousarray(seg_times, dtype=np.float64).reshape(-1)
+        C = np.ascontiguousarray(coeffs, dtype=np.float64)
+        B = so.shape[0] - 1
+        ext = np.zeros((B, _lib.EXTREMA_STRIDE), dtype=np.float64)
+        flags = np.zeros(B, dtype=np.int32)
+        st = self._L.tgms_bounds_batch(self._h, B, _ptr(so), _ptr(T), _ptr(C),
+                                       None if limits is None else ctypes.byref(limits), _ptr(ext), _ptr(flags))
+        if st != _lib.OK:
+            raise TgmsError(st, self.last_error())
+        return ext, flags
+
     def refine(self, seg_offsets, waypoints, seg_times, end_derivs=None, k_T: float = 1.0, eta: float = 0.1,
                iters: int = 10, coeffs: bool = True):
         """Time-allocation refinement on the GPU (include/tgms.h tgms_refine_batch).
@@ -260,6 +277,16 @@ class Solver:
                                                _ptr(d_seg_times), _ptr(d_end_derivs), _ptr(d_coeffs), float(dt),
                                                None if limits is None else ctypes.byref(limits),
                                                _ptr(d_extrema), _ptr(d_flags), ctypes.c_void_p(stream))
+        if st != _lib.OK:
+            raise TgmsError(st, self.last_error())
+
+    def bounds_device(self, B: int, d_seg_offsets, d_seg_times, d_coeffs, limits: Optional[_lib.Limits] = None,
+                      d_extrema=None, d_flags=None, stream: int = 0) -> None:
+        """tgms_bounds_batch_device: d_extrema [B,10] fp64 and / or d_flags [B] int32 (at
+        least one); `limits` is read now, so it may change before the kernel runs."""
+        st = self._L.tgms_bounds_batch_device(self._h, int(B), _ptr(d_seg_offsets), _ptr(d_seg_times),
+                                              _ptr(d_coeffs), None if limits is None else ctypes.byref(limits),
+                                              _ptr(d_extrema), _ptr(d_flags), ctypes.c_void_p(stream))
         if st != _lib.OK:
             raise TgmsError(st, self.last_error())
 
