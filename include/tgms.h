@@ -292,6 +292,64 @@ tgms_status tgms_bounds_batch(tgms_handle* h, int32_t B, const int32_t* seg_offs
                               const double* seg_times, const double* coeffs,
                               const tgms_limits* limits, double* extrema, int32_t* flags);
 
+/* ---- continuous swarm separation: closest approach of trajectory pairs ----
+ * All in fp64.  Trajectory b lives on the global interval [t0_b, t0_b + D_b]: t0_b =
+ * start_times[b] (0 when start_times == NULL) and D_b is the left-to-right prefix sum of its
+ * seg_times, the `duration` of the extrema record; its knot m is at t0_b + (the prefix sum of
+ * its first m times).  Outside that interval the vehicle holds the nearest end point, p(0) of
+ * its first segment or p(T) of its last, so the distance of a pair (i, j)
+ *     d(t) = sqrt(sum_a (s_a (p_i,a(t) - p_j,a(t)))^2)
+ * is defined for all t and is constant outside the window [min(t0_i, t0_j), max(end_i,
+ * end_j)], which is what is searched.  `scale` = s[3] is a host array read at call time (its
+ * values travel as kernel arguments, like tgms_limits): the per-axis scale of the usual
+ * downwash ellipsoid.  NULL means 1, 1, 1; an entry that is not finite and > 0 is
+ * TGMS_ERR_INVALID_ARG.
+ *   Per pair one record of TGMS_SEP_STRIDE doubles, d_min t_min, and an int32 flag word.  d_min
+ * is the minimum of d over the window; t_min is a global time in the window at which the
+ * returned d_min is attained (which one among ties is unspecified).  On every interval
+ * between consecutive knots of either trajectory d^2 is a polynomial of degree <= 14, so the
+ * minimum is the least value at the interval ends and at the stationary points, which the
+ * derivative ladder of the bounds call locates: O(M_i + M_j) work per pair, no resolution.
+ *   pairs is int32 [P][2], P an int64_t.  pairs == NULL means every unordered pair in the
+ * order (0,1), (0,2), ..., (0,B-1), (1,2), ...; P must then equal B (B - 1) / 2, else
+ * TGMS_ERR_INVALID_ARG; the index is decoded on the device and no pair list exists anywhere.
+ * (i, i) is a valid pair, and identical trajectories with equal start times give d_min == 0.0
+ * exactly: a value is always the difference of the two trajectories' own polynomials at their
+ * own local times.
+ *   flags: TGMS_SEP_CLOSE when d_min < r_min (strict, on the stored value); r_min <= 0 checks
+ * nothing, a NaN r_min is TGMS_ERR_INVALID_ARG.  A pair gets TGMS_SEP_NONFINITE alone and an
+ * all-NaN record when an index is outside 0..B-1 (nothing is read for it), when either
+ * trajectory has a non-finite coefficient, time or start time or a T that is not > 0, when,
+ * in the device call, either has a segment count outside 1..TGMS_MAX_SEGMENTS, or when the
+ * result is not finite.  Other pairs are unaffected.
+ *   Accuracy, on the squared distance since d itself is ill-conditioned near 0:
+ *     |d_min^2 - d_true^2| <= 1e-9 * L^2,
+ * L the largest scaled coordinate magnitude either trajectory reaches.  As for the bounds
+ * this is an fp64 evaluation at located stationary points, not a certificate; a touch of the
+ * derivative without a sign change may be skipped.
+ *   At least one of sep / flags must be non-NULL; fp64 device arrays are 16-byte aligned; P ==
+ * 0 is TGMS_OK and launches nothing.  tgms_separation_batch_device is one kernel launch with
+ * no host plan and no handle scratch, so it may be captured into a HIP graph for any batch.
+ * On a multi handle it runs on device 0; on a host handle it returns TGMS_ERR_UNSUPPORTED.
+ * tgms_separation_batch on a host handle computes on the calling thread (the same algorithm;
+ * host and device agree to the accuracy above, not to the bit); on a GPU handle it does one
+ * upload, the launch and one download (records and flags in one workspace region), like
+ * tgms_bounds_batch. */
+#define TGMS_SEP_STRIDE 2
+#define TGMS_SEP_CLOSE 1      /* d_min < r_min */
+#define TGMS_SEP_NONFINITE 16 /* a bad index, segment count, time, coefficient or result */
+tgms_status tgms_separation_batch_device(tgms_handle* h, int32_t B, const int32_t* d_seg_offsets,
+                                         const double* d_seg_times, const double* d_coeffs,
+                                         const double* d_start_times /* [B], nullable */, int64_t P,
+                                         const int32_t* d_pairs /* [P][2], nullable: all pairs */,
+                                         const double* scale /* host [3], nullable */, double r_min,
+                                         double* d_sep /* [P][TGMS_SEP_STRIDE], nullable */,
+                                         int32_t* d_flags /* [P], nullable */, void* stream);
+tgms_status tgms_separation_batch(tgms_handle* h, int32_t B, const int32_t* seg_offsets,
+                                  const double* seg_times, const double* coeffs, const double* start_times,
+                                  int64_t P, const int32_t* pairs, const double* scale, double r_min,
+                                  double* sep, int32_t* flags);
+
 /* ---- multi-GPU ----
  * One process drives devices 0 .. device_count-1 through one handle that owns one RCCL
  * communicator per device (ncclCommInitAll, rccl.h:236; RCCL is loaded here, not at

@@ -51,7 +51,7 @@ namespace bounds {
 
 constexpr int BISECTIONS = 40;
 
-// n (n-1) ... (n-m+1); exact in fp64 for n <= 12
+// n (n-1) ... (n-m+1); exact in fp64 for n <= 18 (18! < 2^53; the callers need n <= 13)
 constexpr double ffact(int n, int m) {
     double r = 1.0;
     for (int i = 0; i < m; ++i) r *= (double)(n - i);

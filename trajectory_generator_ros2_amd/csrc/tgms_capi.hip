@@ -13,6 +13,7 @@
 #include "tgms_internal.h"
 #include "tgms_plan.h"
 #include "tgms_host.h"
+#include "tgms_separation_core.h"
 
 #include <dlfcn.h>
 #include <hip/hip_runtime.h>
@@ -1992,6 +1993,130 @@ tgms_status tgms_bounds_batch(tgms_handle* h, int32_t B, const int32_t* so, cons
         return TGMS_OK;
     }
     if (dExt) TGMS_HIP(h, hipMemcpyAsync(extrema, dExt, nExt, hipMemcpyDeviceToHost, st));
+    if (dFl) TGMS_HIP(h, hipMemcpyAsync(flags, dFl, nFl, hipMemcpyDeviceToHost, st));
+    TGMS_HIP(h, hipStreamSynchronize(st));
+    return TGMS_OK;
+}
+
+// ---- continuous swarm separation: closest approach of trajectory pairs ----
+
+// The scale a launch carries: the caller's, or 1, 1, 1 for NULL.
+static bool resolve_scale(const double* in, double (&out)[3]) {
+    for (int a = 0; a < 3; ++a) {
+        out[a] = in ? in[a] : 1.0;
+        if (!(out[a] > 0.0) || !std::isfinite(out[a])) return false;
+    }
+    return true;
+}
+
+// What both calls check before they look at a pointer.
+static tgms_status check_separation(tgms_handle* h, int32_t B, int64_t P, const int32_t* pairs, const double* scale,
+                                    double r_min, const void* sep, const void* flags, double (&sc)[3]) {
+    if (B < 0 || P < 0) return set_err(h, TGMS_ERR_INVALID_ARG, "bad B or P");
+    if (!pairs && P != (int64_t)B * ((int64_t)B - 1) / 2)
+        return set_err(h, TGMS_ERR_INVALID_ARG, "pairs == NULL needs P == B (B - 1) / 2");
+    if (!resolve_scale(scale, sc)) return set_err(h, TGMS_ERR_INVALID_ARG, "scale entries must be finite and > 0");
+    if (std::isnan(r_min)) return set_err(h, TGMS_ERR_INVALID_ARG, "r_min is NaN");
+    if (!sep && !flags) return set_err(h, TGMS_ERR_INVALID_ARG, "sep and flags both NULL");
+    return TGMS_OK;
+}
+
+tgms_status tgms_separation_batch_device(tgms_handle* h, int32_t B, const int32_t* d_so, const double* dT,
+                                         const double* dC, const double* d_start_times, int64_t P,
+                                         const int32_t* d_pairs, const double* scale, double r_min, double* d_sep,
+                                         int32_t* d_flags, void* stream) {
+    if (!h) return TGMS_ERR_INVALID_ARG;
+    if (h->host)
+        return set_err(h, TGMS_ERR_UNSUPPORTED, "tgms_separation_batch_device needs a GPU handle (tgms_create)");
+    h->last_error.clear();
+    double sc[3];
+    const tgms_status s = check_separation(h, B, P, d_pairs, scale, r_min, d_sep, d_flags, sc);
+    if (s != TGMS_OK) return s;
+    if (P == 0) return TGMS_OK;
+    if (!d_so || !dT || !dC) return set_err(h, TGMS_ERR_INVALID_ARG, "NULL device pointer");
+    TGMS_CHECK_ALIGNED(h, dT, dC, d_start_times, d_sep);
+    TGMS_HIP(h, tgms::launch_separation(B, d_so, dT, dC, d_start_times, P, d_pairs, sc, r_min, d_sep, d_flags,
+                                        static_cast<hipStream_t>(stream)));
+    return TGMS_OK;
+}
+
+tgms_status tgms_separation_batch(tgms_handle* h, int32_t B, const int32_t* so, const double* seg_times,
+                                  const double* coeffs, const double* start_times, int64_t P, const int32_t* pairs,
+                                  const double* scale, double r_min, double* sep, int32_t* flags) {
+    if (!h) return TGMS_ERR_INVALID_ARG;
+    h->last_error.clear();
+    tgms_status s = check_offsets(h, B, so, TGMS_MAX_SEGMENTS, nullptr, nullptr);
+    if (s != TGMS_OK) return s;
+    double sc[3];
+    s = check_separation(h, B, P, pairs, scale, r_min, sep, flags, sc);
+    if (s != TGMS_OK) return s;
+    if (P == 0) return TGMS_OK;
+    if (!seg_times || !coeffs) return set_err(h, TGMS_ERR_INVALID_ARG, "NULL pointer");
+    if (h->host) {
+        for (int64_t n = 0; n < P; ++n) {
+            int32_t ij[2];
+            if (pairs) {
+                ij[0] = pairs[2 * n];
+                ij[1] = pairs[2 * n + 1];
+            } else {
+                tgms::separation::decode_pair(n, B, P, ij[0], ij[1]);
+            }
+            int M[2] = {0, 0};
+            int64_t s0[2] = {0, 0};
+            double t0[2] = {0.0, 0.0};
+            for (int k = 0; k < 2; ++k)
+                if (ij[k] >= 0 && ij[k] < B) {  // else nothing is read: M == 0 rules the pair out
+                    s0[k] = so[ij[k]];
+                    M[k] = so[ij[k] + 1] - so[ij[k]];
+                    t0[k] = start_times ? start_times[ij[k]] : 0.0;
+                }
+            double rec[TGMS_SEP_STRIDE];
+            const int fl = tgms::host::separation(M[0], coeffs + s0[0] * 24, seg_times + s0[0], t0[0], M[1],
+                                                  coeffs + s0[1] * 24, seg_times + s0[1], t0[1], sc, r_min, rec);
+            if (sep) std::copy(rec, rec + TGMS_SEP_STRIDE, sep + n * TGMS_SEP_STRIDE);
+            if (flags) flags[n] = fl;
+        }
+        return TGMS_OK;
+    }
+    TGMS_HIP(h, hipSetDevice(h->device));
+    const size_t S = (size_t)so[B];
+    const size_t nT = S, nC = S * 24, nT0 = start_times ? (size_t)B : 0, nP = pairs ? (size_t)P * 2 : 0;
+    size_t off = 0;
+    const size_t oT = off; off = align256(off + nT * 8);
+    const size_t oC = off; off = align256(off + nC * 8);
+    const size_t oT0 = off; off = align256(off + nT0 * 8);
+    const size_t oSo = off; off = align256(off + (size_t)(B + 1) * 4);
+    const size_t oP = off; off = align256(off + nP * 4);
+    // both results in one region, the flags right behind the records: one download
+    const size_t nSep = (size_t)P * TGMS_SEP_STRIDE * 8, nFl = (size_t)P * 4;
+    const size_t oSep = off; off = align256(off + nSep + nFl);
+    const size_t oFl = oSep + nSep;
+    s = ensure_ws(h, off);
+    if (s != TGMS_OK) return s;
+    char* base = static_cast<char*>(h->d_ws);
+    double* dT = reinterpret_cast<double*>(base + oT);
+    double* dC = reinterpret_cast<double*>(base + oC);
+    double* dT0 = start_times ? reinterpret_cast<double*>(base + oT0) : nullptr;
+    int32_t* dSo = reinterpret_cast<int32_t*>(base + oSo);
+    int32_t* dP = pairs ? reinterpret_cast<int32_t*>(base + oP) : nullptr;
+    double* dSep = sep ? reinterpret_cast<double*>(base + oSep) : nullptr;
+    int32_t* dFl = flags ? reinterpret_cast<int32_t*>(base + oFl) : nullptr;
+    hipStream_t st = h->stream;
+    TGMS_HIP(h, hipMemcpyAsync(dT, seg_times, nT * 8, hipMemcpyHostToDevice, st));
+    TGMS_HIP(h, hipMemcpyAsync(dC, coeffs, nC * 8, hipMemcpyHostToDevice, st));
+    if (dT0) TGMS_HIP(h, hipMemcpyAsync(dT0, start_times, nT0 * 8, hipMemcpyHostToDevice, st));
+    TGMS_HIP(h, hipMemcpyAsync(dSo, so, (size_t)(B + 1) * 4, hipMemcpyHostToDevice, st));
+    if (dP) TGMS_HIP(h, hipMemcpyAsync(dP, pairs, nP * 4, hipMemcpyHostToDevice, st));
+    TGMS_HIP(h, tgms::launch_separation(B, dSo, dT, dC, dT0, P, dP, sc, r_min, dSep, dFl, st));
+    if (dSep && dFl) {  // 16 B + 4 B per pair in one copy, split on the host
+        std::vector<char> res(nSep + nFl);
+        TGMS_HIP(h, hipMemcpyAsync(res.data(), base + oSep, nSep + nFl, hipMemcpyDeviceToHost, st));
+        TGMS_HIP(h, hipStreamSynchronize(st));
+        std::memcpy(sep, res.data(), nSep);
+        std::memcpy(flags, res.data() + nSep, nFl);
+        return TGMS_OK;
+    }
+    if (dSep) TGMS_HIP(h, hipMemcpyAsync(sep, dSep, nSep, hipMemcpyDeviceToHost, st));
     if (dFl) TGMS_HIP(h, hipMemcpyAsync(flags, dFl, nFl, hipMemcpyDeviceToHost, st));
     TGMS_HIP(h, hipStreamSynchronize(st));
     return TGMS_OK;

@@ -24,6 +24,7 @@
 #include <cmath>
 
 #include "tgms_bounds_core.h"
+#include "tgms_separation_core.h"
 
 namespace tgms {
 namespace host {
@@ -331,6 +332,49 @@ int bounds(int M, const double* C, const double* T, const tgms_limits* lim, doub
     double r[TGMS_EXTREMA_STRIDE];
     const int fl = tgms::bounds::finish(lo, hi, n2, acc, bad, lim ? *lim : none, r);
     for (int q = 0; q < TGMS_EXTREMA_STRIDE; ++q) rec[q] = r[q];
+    return fl;
+}
+
+int separation(int Mi, const double* ci, const double* Ti, double t0i, int Mj, const double* cj, const double* Tj,
+               double t0j, const double* scale, double r_min, double* rec) {
+    namespace sp = tgms::separation;
+    const int M[2] = {Mi, Mj};
+    const double* T[2] = {Ti, Tj};
+    const double* C[2] = {ci, cj};
+    const double t0[2] = {t0i, t0j};
+    const double sc[3] = {scale[0], scale[1], scale[2]};
+    double kn[2][sp::MAX_KNOTS], tl[2] = {0.0, 0.0};
+    bool bad = false;
+    for (int s = 0; s < 2; ++s) {
+        bad = bad || M[s] < 1 || M[s] > TGMS_MAX_SEGMENTS || !finite(t0[s]);
+        if (bad) break;
+        double acc = 0.0;
+        kn[s][0] = t0[s];
+        for (int m = 0; m < M[s]; ++m) {
+            tl[s] = T[s][m];
+            bad = bad || !(tl[s] > 0.0);
+            acc += tl[s];  // the same order as the extrema record's duration
+            kn[s][m + 1] = t0[s] + acc;
+            bad = bad || !finite(kn[s][m + 1]);
+        }
+    }
+    double best = HUGE_VAL, at = 0.0;
+    if (!bad) {
+        double mk[sp::MAX_MERGED];
+        int32_t sg[sp::MAX_INTERVALS];
+        sp::merge_knots(kn[0], Mi, kn[1], Mj, mk, sg);
+        for (int q = 0; q < Mi + Mj + 1; ++q) {
+            const double a = mk[q], b = mk[q + 1], h = b - a;
+            const sp::Side si = sp::side_of((sg[q] & 255) - 1, Mi, kn[0], tl[0], a, h);
+            const sp::Side sj = sp::side_of((sg[q] >> 8) - 1, Mj, kn[1], tl[1], a, h);
+            double d2, u;
+            sp::interval_item(C[0] + si.seg * 24, si, C[1] + sj.seg * 24, sj, sc, h, d2, u);
+            sp::fold(d2, std::fmin(std::fma(h, u, a), b), best, at, bad);
+        }
+    }
+    double r[TGMS_SEP_STRIDE];
+    const int fl = sp::finish(best, at, bad, r_min, r);
+    for (int q = 0; q < TGMS_SEP_STRIDE; ++q) rec[q] = r[q];
     return fl;
 }
 

@@ -29,5 +29,12 @@ int extrema(int M, const double* coeffs, const double* seg_times, const double* 
 // algorithm is the kernel's (tgms_bounds_core.h), one item after the other.
 int bounds(int M, const double* coeffs, const double* seg_times, const tgms_limits* lim, double* rec);
 
+// Closest approach of one pair (include/tgms.h tgms_separation_batch): trajectory i has Mi
+// segments (coeffs ci, times Ti) and starts at t0i, likewise j.  Mi or Mj == 0 says that the
+// pair's index was out of range.  rec [TGMS_SEP_STRIDE] = d_min t_min; returns the TGMS_SEP_*
+// bits.  The algorithm is the kernel's (tgms_separation_core.h), one interval after the other.
+int separation(int Mi, const double* ci, const double* Ti, double t0i, int Mj, const double* cj, const double* Tj,
+               double t0j, const double* scale, double r_min, double* rec);
+
 }  // namespace host
 }  // namespace tgms

@@ -138,4 +138,11 @@ hipError_t launch_extrema(int32_t B, const int32_t* seg_offsets, const double* W
 // polynomials' stationary points, no dt; a wavefront per tile of 4 trajectories, one launch.
 hipError_t launch_bounds(int32_t B, const int32_t* seg_offsets, const double* T, const double* C,
                          const tgms_limits& lim, double* ext, int32_t* flags, hipStream_t stream);
+
+// Continuous swarm separation (tgms_separation.hip): per pair the closest approach d_min t_min
+// into sep [P][TGMS_SEP_STRIDE] and flags [P] (either nullable); pairs NULL: every unordered
+// pair, decoded on the device.  A wavefront per tile of 16 pairs, one launch.
+hipError_t launch_separation(int32_t B, const int32_t* seg_offsets, const double* T, const double* C,
+                             const double* start_times, int64_t P, const int32_t* pairs, const double (&scale)[3],
+                             double r_min, double* sep, int32_t* flags, hipStream_t stream);
 }  // namespace tgms

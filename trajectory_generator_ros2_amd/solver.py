@@ -172,6 +172,31 @@ class Solver:
             raise TgmsError(st, self.last_error())
         return ext, flags
 
+    def separation(self, seg_offsets, seg_times, coeffs, pairs=None, start_times=None, scale=None,
+                   r_min: float = 0.0) -> Tuple[np.ndarray, np.ndarray]:
+        """Continuous swarm separation (include/tgms.h tgms_separation_batch): per pair the
+        closest approach (sep [P,2] = d_min t_min, flags [P] of SEP_* bits).  pairs: int32
+        [P,2], or None for every unordered pair (0,1), (0,2), ..., (1,2), ...; start_times [B]
+        (None: all 0); scale: the three per-axis factors (None: 1, 1, 1)."""
+        so = np.ascontiguousarray(seg_offsets, dtype=np.int32)
+        T = np.ascontiguousarray(seg_times, dtype=np.float64).reshape(-1)
+        C = np.ascontiguousarray(coeffs, dtype=np.float64)
+        t0 = None if start_times is None else np.ascontiguousarray(start_times, dtype=np.float64).reshape(-1)
+        sc = None if scale is None else np.ascontiguousarray(scale, dtype=np.float64).reshape(3)
+        B = so.shape[0] - 1
+        if pairs is None:
+            pr, P = None, B * (B - 1) // 2
+        else:
+            pr = np.ascontiguousarray(pairs, dtype=np.int32).reshape(-1, 2)
+            P = pr.shape[0]
+        sep = np.full((P, _lib.SEP_STRIDE), np.nan, dtype=np.float64)
+        flags = np.full(P, -1, dtype=np.int32)
+        st = self._L.tgms_separation_batch(self._h, B, _ptr(so), _ptr(T), _ptr(C), _ptr(t0), P, _ptr(pr), _ptr(sc),
+                                           float(r_min), _ptr(sep), _ptr(flags))
+        if st != _lib.OK:
+            raise TgmsError(st, self.last_error())
+        return sep, flags
+
     def refine(self, seg_offsets, waypoints, seg_times, end_derivs=None, k_T: float = 1.0, eta: float = 0.1,
                iters: int = 10, coeffs: bool = True):
         """Time-allocation refinement on the GPU (include/tgms.h tgms_refine_batch).
@@ -287,6 +312,20 @@ class Solver:
         st = self._L.tgms_bounds_batch_device(self._h, int(B), _ptr(d_seg_offsets), _ptr(d_seg_times),
                                               _ptr(d_coeffs), None if limits is None else ctypes.byref(limits),
                                               _ptr(d_extrema), _ptr(d_flags), ctypes.c_void_p(stream))
+        if st != _lib.OK:
+            raise TgmsError(st, self.last_error())
+
+    def separation_device(self, B: int, d_seg_offsets, d_seg_times, d_coeffs, P: int, d_pairs=None,
+                          d_start_times=None, scale=None, r_min: float = 0.0, d_sep=None, d_flags=None,
+                          stream: int = 0) -> None:
+        """tgms_separation_batch_device: d_sep [P,2] fp64 and / or d_flags [P] int32 (at least
+        one); d_pairs int32 [P,2] or None for all pairs (P = B (B - 1) / 2); `scale` (host,
+        three values or None) and r_min are read now."""
+        sc = None if scale is None else np.ascontiguousarray(scale, dtype=np.float64).reshape(3)
+        st = self._L.tgms_separation_batch_device(self._h, int(B), _ptr(d_seg_offsets), _ptr(d_seg_times),
+                                                  _ptr(d_coeffs), _ptr(d_start_times), int(P), _ptr(d_pairs),
+                                                  _ptr(sc), float(r_min), _ptr(d_sep), _ptr(d_flags),
+                                                  ctypes.c_void_p(stream))
         if st != _lib.OK:
             raise TgmsError(st, self.last_error())
 
