@@ -149,6 +149,125 @@ tgms_status ensure_ws(tgms_handle* h, size_t bytes) {
     return TGMS_OK;
 }
 
+// Every entry point's opening: a handle, a GPU handle where `gpu_only` names the entry point
+// (the host backend has no device path), and no error left over from an earlier call.
+tgms_status enter(tgms_handle* h, const char* gpu_only = nullptr) {
+    if (!h) return TGMS_ERR_INVALID_ARG;
+    if (gpu_only && h->host)
+        return set_err(h, TGMS_ERR_UNSUPPORTED, std::string(gpu_only) + " needs a GPU handle (tgms_create)");
+    h->last_error.clear();
+    return TGMS_OK;
+}
+
+// ---- staging of the host-pointer (blocking) entry points ----
+// Such a call lays its device arrays out in the handle's workspace, uploads its inputs on the
+// handle's stream, launches, and downloads.  It declares its regions in layout order
+// (input / output below, counts in elements) and stage() does the rest.  Every region starts
+// 256-byte aligned (the kernels move fp64 data in 16-byte pieces); a region without elements
+// takes no space, gets nullptr and no copy.
+struct Region {
+    void* slot;                      // the caller's T*: receives the region's device pointer
+    void (*set)(void* slot, char*);  // the typed store into it
+    const void* src;                 // host data to upload; nullptr: an output or scratch
+    size_t bytes;
+};
+template <class T>
+void set_slot(void* slot, char* p) {
+    *static_cast<T**>(slot) = reinterpret_cast<T*>(p);
+}
+template <class T>
+Region input(T** dev, const T* src, size_t n) {  // absent when src is NULL
+    return {dev, set_slot<T>, src, src ? n * sizeof(T) : 0};
+}
+template <class T>
+Region output(T** dev, size_t n) {
+    return {dev, set_slot<T>, nullptr, n * sizeof(T)};
+}
+
+tgms_status stage(tgms_handle* h, std::initializer_list<Region> regions) {
+    TGMS_HIP(h, hipSetDevice(h->device));
+    size_t off = 0;
+    for (const Region& r : regions) off = align256(off + r.bytes);
+    const tgms_status s = ensure_ws(h, off);
+    if (s != TGMS_OK) return s;
+    char* const base = static_cast<char*>(h->d_ws);
+    off = 0;
+    for (const Region& r : regions) {
+        char* const d = r.bytes ? base + off : nullptr;
+        r.set(r.slot, d);
+        if (d && r.src) TGMS_HIP(h, hipMemcpyAsync(d, r.src, r.bytes, hipMemcpyHostToDevice, h->stream));
+        off = align256(off + r.bytes);
+    }
+    return TGMS_OK;
+}
+
+// Enqueues the download of n elements on the handle's stream.
+template <class T>
+hipError_t fetch(tgms_handle* h, T* host, const T* dev, size_t n) {
+    return hipMemcpyAsync(host, dev, n * sizeof(T), hipMemcpyDeviceToHost, h->stream);
+}
+
+// The two results of a check, fp64 records and int32 flags, in one region with the flags
+// right behind the records (no rounding between them), so that one copy fetches both.  The
+// caller may ask for either alone: the kernel then gets nullptr for the other.
+struct ResultPair {
+    double* rec;  // host destinations, at most one of them NULL
+    int32_t* flags;
+    size_t n_rec, n_flags;  // elements
+    char* d = nullptr;      // the region (stage)
+    size_t rec_bytes() const { return n_rec * sizeof(double); }
+    size_t flag_bytes() const { return n_flags * sizeof(int32_t); }
+    double* d_rec() const { return rec ? reinterpret_cast<double*>(d) : nullptr; }
+    int32_t* d_flags() const { return flags ? reinterpret_cast<int32_t*>(d + rec_bytes()) : nullptr; }
+};
+Region output(ResultPair* p) { return output(&p->d, p->rec_bytes() + p->flag_bytes()); }
+
+// Downloads what the caller asked for and waits for it.
+tgms_status download(tgms_handle* h, const ResultPair& p) {
+    if (p.rec && p.flags) {  // both in one copy, split on the host
+        std::vector<char> both(p.rec_bytes() + p.flag_bytes());
+        TGMS_HIP(h, fetch(h, both.data(), p.d, both.size()));
+        TGMS_HIP(h, hipStreamSynchronize(h->stream));
+        std::memcpy(p.rec, both.data(), p.rec_bytes());
+        std::memcpy(p.flags, both.data() + p.rec_bytes(), p.flag_bytes());
+        return TGMS_OK;
+    }
+    if (p.rec) TGMS_HIP(h, fetch(h, p.rec, p.d_rec(), p.n_rec));
+    if (p.flags) TGMS_HIP(h, fetch(h, p.flags, p.d_flags(), p.n_flags));
+    TGMS_HIP(h, hipStreamSynchronize(h->stream));
+    return TGMS_OK;
+}
+
+// The worst per-trajectory status of a batch; `message`: the first trajectory that has it
+// goes into last_error.
+tgms_status worst_status(tgms_handle* h, const int32_t* st, int32_t B, bool message) {
+    int worst = TGMS_OK;
+    for (int32_t b = 0; b < B; ++b) worst = std::max(worst, (int)st[b]);
+    if (worst != TGMS_OK && message) {
+        for (int32_t b = 0; b < B; ++b)
+            if (st[b] == worst) {
+                char buf[160];
+                snprintf(buf, sizeof buf, "trajectory %d: %s", b, tgms_status_string(worst));
+                h->last_error = buf;
+                break;
+            }
+    }
+    return (tgms_status)worst;
+}
+
+// The end of a blocking solve: the statuses go to the caller (or, for status == NULL, into a
+// temporary), the stream is drained, and the worst status is the call's result.
+tgms_status finish_status(tgms_handle* h, const int32_t* dSt, int32_t* status, int32_t B, bool message) {
+    std::vector<int32_t> tmp;
+    if (!status) {
+        tmp.resize(B);
+        status = tmp.data();
+    }
+    TGMS_HIP(h, fetch(h, status, dSt, (size_t)B));
+    TGMS_HIP(h, hipStreamSynchronize(h->stream));
+    return worst_status(h, status, B, message);
+}
+
 // True while `stream` is being captured into a HIP graph.
 bool capturing(hipStream_t stream) {
     hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
@@ -174,6 +293,13 @@ tgms_status scratch_release(tgms_handle* h, hipStream_t stream) {
         h->band_unmarked = false;
     }
     return TGMS_OK;
+}
+
+// After a dispatch that returned `s`: released on failure too (a band call that launched
+// must still write its marker); the first error is the result.
+tgms_status scratch_release(tgms_handle* h, hipStream_t stream, tgms_status s) {
+    const tgms_status r = scratch_release(h, stream);
+    return s != TGMS_OK ? s : r;
 }
 
 tgms_status no_capture(tgms_handle* h, hipStream_t stream, const char* what) {
@@ -1316,21 +1442,6 @@ tgms_status create_multi_ctx(tgms_handle* h, int n) {
     return TGMS_OK;
 }
 
-tgms_status worst_status(tgms_handle* h, const int32_t* st, int32_t B) {
-    int worst = TGMS_OK;
-    for (int32_t b = 0; b < B; ++b) worst = std::max(worst, (int)st[b]);
-    if (worst != TGMS_OK) {
-        for (int32_t b = 0; b < B; ++b)
-            if (st[b] == worst) {
-                char buf[160];
-                snprintf(buf, sizeof buf, "trajectory %d: %s", b, tgms_status_string(worst));
-                h->last_error = buf;
-                break;
-            }
-    }
-    return (tgms_status)worst;
-}
-
 }  // namespace
 
 extern "C" {
@@ -1439,8 +1550,7 @@ tgms_status tgms_set_method(tgms_handle* h, int method) {
 tgms_status tgms_solve_batch(tgms_handle* h, int32_t B, const int32_t* so, const double* waypoints,
                              const double* seg_times, const double* end_derivs, double* coeffs,
                              int32_t* status) {
-    if (!h) return TGMS_ERR_INVALID_ARG;
-    h->last_error.clear();
+    if (tgms_status e = enter(h); e != TGMS_OK) return e;
     Plan plan;
     tgms_status s = check_offsets(h, B, so, max_m_for(h), &plan.counts, &plan.uniform_m);
     if (s != TGMS_OK) return s;
@@ -1461,61 +1571,21 @@ tgms_status tgms_solve_batch(tgms_handle* h, int32_t B, const int32_t* so, const
         }
         return (tgms_status)worst;
     }
-    TGMS_HIP(h, hipSetDevice(h->device));
     const size_t S = (size_t)so[B];
-    const size_t nW = (S + B) * 3, nT = S, nED = end_derivs ? (size_t)B * 18 : 0, nC = S * 24;
-    size_t off = 0;
-    const size_t oW = off; off = align256(off + nW * 8);
-    const size_t oT = off; off = align256(off + nT * 8);
-    const size_t oED = off; off = align256(off + nED * 8);
-    const size_t oC = off; off = align256(off + nC * 8);
-    const size_t oSt = off; off = align256(off + (size_t)B * 4);
-    const size_t oSo = off; off = align256(off + (size_t)(B + 1) * 4);
-    s = ensure_ws(h, off);
+    double *dW, *dT, *dED, *dC;
+    int32_t *dSt, *dSo;
+    s = stage(h, {input(&dW, waypoints, (S + B) * 3), input(&dT, seg_times, S), input(&dED, end_derivs, (size_t)B * 18),
+                  output(&dC, S * 24), output(&dSt, (size_t)B), input(&dSo, so, (size_t)B + 1)});
     if (s != TGMS_OK) return s;
-    char* base = static_cast<char*>(h->d_ws);
-    double* dW = reinterpret_cast<double*>(base + oW);
-    double* dT = reinterpret_cast<double*>(base + oT);
-    double* dED = end_derivs ? reinterpret_cast<double*>(base + oED) : nullptr;
-    double* dC = reinterpret_cast<double*>(base + oC);
-    int32_t* dSt = reinterpret_cast<int32_t*>(base + oSt);
-    int32_t* dSo = reinterpret_cast<int32_t*>(base + oSo);
     hipStream_t st = h->stream;
-    TGMS_HIP(h, hipMemcpyAsync(dW, waypoints, nW * 8, hipMemcpyHostToDevice, st));
-    TGMS_HIP(h, hipMemcpyAsync(dT, seg_times, nT * 8, hipMemcpyHostToDevice, st));
-    if (dED) TGMS_HIP(h, hipMemcpyAsync(dED, end_derivs, nED * 8, hipMemcpyHostToDevice, st));
-    TGMS_HIP(h, hipMemcpyAsync(dSo, so, (size_t)(B + 1) * 4, hipMemcpyHostToDevice, st));
     s = scratch_acquire(h, st);
     if (s != TGMS_OK) return s;
     s = plan_upload(h, B, so, &plan, st);
     if (s != TGMS_OK) return s;
-    s = dispatch(h, plan, B, dSo, dW, dT, dED, dC, dSt, st);
-    {  // released on failure too: a band call that launched must still write its marker
-        const tgms_status r_ = scratch_release(h, st);
-        if (s == TGMS_OK) s = r_;
-    }
+    s = scratch_release(h, st, dispatch(h, plan, B, dSo, dW, dT, dED, dC, dSt, st));
     if (s != TGMS_OK) return s;
-    TGMS_HIP(h, hipMemcpyAsync(coeffs, dC, nC * 8, hipMemcpyDeviceToHost, st));
-    std::vector<int32_t> hst;
-    int32_t* stout = status;
-    if (!stout) {
-        hst.resize(B);
-        stout = hst.data();
-    }
-    TGMS_HIP(h, hipMemcpyAsync(stout, dSt, (size_t)B * 4, hipMemcpyDeviceToHost, st));
-    TGMS_HIP(h, hipStreamSynchronize(st));
-    int worst = TGMS_OK;
-    for (int32_t b = 0; b < B; ++b) worst = std::max(worst, (int)stout[b]);
-    if (worst != TGMS_OK) {
-        for (int32_t b = 0; b < B; ++b)
-            if (stout[b] == worst) {
-                char buf[160];
-                snprintf(buf, sizeof buf, "trajectory %d: %s", b, tgms_status_string(worst));
-                h->last_error = buf;
-                break;
-            }
-    }
-    return (tgms_status)worst;
+    TGMS_HIP(h, fetch(h, coeffs, dC, S * 24));
+    return finish_status(h, dSt, status, B, true);
 }
 
 // Device buffers: the kernels move fp64 data in 16-B pieces (double2 loads/stores,
@@ -1535,9 +1605,7 @@ static bool misaligned(std::initializer_list<const void*> ps) {
 tgms_status tgms_solve_uniform_device(tgms_handle* h, int32_t B, int32_t M, const double* dW,
                                       const double* dT, const double* dED, double* dC,
                                       int32_t* dSt, void* stream) {
-    if (!h) return TGMS_ERR_INVALID_ARG;
-    if (h->host) return set_err(h, TGMS_ERR_UNSUPPORTED, "tgms_solve_uniform_device needs a GPU handle (tgms_create)");
-    h->last_error.clear();
+    if (tgms_status e = enter(h, __func__); e != TGMS_OK) return e;
     if (B < 0 || M < 1 || M > max_m_for(h))
         return set_err(h, M > TGMS_MAX_SEGMENTS || M < 1 || B < 0 ? TGMS_ERR_INVALID_ARG : TGMS_ERR_UNSUPPORTED,
                        "bad B or M for this method");
@@ -1566,9 +1634,7 @@ tgms_status tgms_solve_uniform_device(tgms_handle* h, int32_t B, int32_t M, cons
 tgms_status tgms_solve_batch_device(tgms_handle* h, int32_t B, const int32_t* h_so,
                                     const int32_t* d_so, const double* dW, const double* dT,
                                     const double* dED, double* dC, int32_t* dSt, void* stream) {
-    if (!h) return TGMS_ERR_INVALID_ARG;
-    if (h->host) return set_err(h, TGMS_ERR_UNSUPPORTED, "tgms_solve_batch_device needs a GPU handle (tgms_create)");
-    h->last_error.clear();
+    if (tgms_status e = enter(h, __func__); e != TGMS_OK) return e;
     Plan plan;
     tgms_status s = check_offsets(h, B, h_so, max_m_for(h), &plan.counts, &plan.uniform_m);
     if (s != TGMS_OK) return s;
@@ -1588,9 +1654,7 @@ tgms_status tgms_solve_batch_device(tgms_handle* h, int32_t B, const int32_t* h_
 tgms_status tgms_refine_uniform_device(tgms_handle* h, int32_t B, int32_t M, const double* dW, const double* dT,
                                        const double* dED, double k_T, double eta, double* dT_out, double* d_cost,
                                        int32_t* dSt, void* stream) {
-    if (!h) return TGMS_ERR_INVALID_ARG;
-    if (h->host) return set_err(h, TGMS_ERR_UNSUPPORTED, "tgms_refine_uniform_device needs a GPU handle (tgms_create)");
-    h->last_error.clear();
+    if (tgms_status e = enter(h, __func__); e != TGMS_OK) return e;
     tgms_status s = check_refine_args(h, k_T, eta);
     if (s != TGMS_OK) return s;
     if (B < 0 || M < 1 || M > TGMS_MAX_SEGMENTS) return set_err(h, TGMS_ERR_INVALID_ARG, "bad B or M");
@@ -1605,9 +1669,7 @@ tgms_status tgms_refine_uniform_device(tgms_handle* h, int32_t B, int32_t M, con
 tgms_status tgms_refine_batch_device(tgms_handle* h, int32_t B, const int32_t* h_so, const int32_t* d_so,
                                      const double* dW, const double* dT, const double* dED, double k_T, double eta,
                                      double* dT_out, double* d_cost, int32_t* dSt, void* stream) {
-    if (!h) return TGMS_ERR_INVALID_ARG;
-    if (h->host) return set_err(h, TGMS_ERR_UNSUPPORTED, "tgms_refine_batch_device needs a GPU handle (tgms_create)");
-    h->last_error.clear();
+    if (tgms_status e = enter(h, __func__); e != TGMS_OK) return e;
     tgms_status s = check_refine_args(h, k_T, eta);
     if (s != TGMS_OK) return s;
     Plan plan;
@@ -1629,9 +1691,7 @@ tgms_status tgms_refine_batch_device(tgms_handle* h, int32_t B, const int32_t* h
 tgms_status tgms_refine_batch(tgms_handle* h, int32_t B, const int32_t* so, const double* waypoints,
                               double* seg_times, const double* end_derivs, double k_T, double eta, int32_t iters,
                               double* coeffs, double* cost, int32_t* status) {
-    if (!h) return TGMS_ERR_INVALID_ARG;
-    if (h->host) return set_err(h, TGMS_ERR_UNSUPPORTED, "tgms_refine_batch needs a GPU handle (tgms_create)");
-    h->last_error.clear();
+    if (tgms_status e = enter(h, __func__); e != TGMS_OK) return e;
     tgms_status s = check_refine_args(h, k_T, eta);
     if (s != TGMS_OK) return s;
     if (iters < 0) return set_err(h, TGMS_ERR_INVALID_ARG, "iters < 0");
@@ -1640,67 +1700,32 @@ tgms_status tgms_refine_batch(tgms_handle* h, int32_t B, const int32_t* so, cons
     if (s != TGMS_OK) return s;
     if (B == 0) return TGMS_OK;
     if (!waypoints || !seg_times) return set_err(h, TGMS_ERR_INVALID_ARG, "NULL waypoints/seg_times");
-    TGMS_HIP(h, hipSetDevice(h->device));
     const size_t S = (size_t)so[B];
-    const size_t nW = (S + B) * 3, nED = end_derivs ? (size_t)B * 18 : 0, nC = coeffs ? S * 24 : 0;
-    size_t off = 0;
-    const size_t oW = off; off = align256(off + nW * 8);
-    const size_t oT0 = off; off = align256(off + S * 8);
-    const size_t oT1 = off; off = align256(off + S * 8);
-    const size_t oED = off; off = align256(off + nED * 8);
-    const size_t oC = off; off = align256(off + nC * 8);
-    const size_t oCost = off; off = align256(off + (size_t)B * 8);
-    const size_t oSt = off; off = align256(off + (size_t)B * 4);
-    const size_t oSo = off; off = align256(off + (size_t)(B + 1) * 4);
-    s = ensure_ws(h, off);
+    double *dW, *dT[2], *dED, *dC, *dCost;  // dT: the loop's two time buffers; dC: only if asked for
+    int32_t *dSt, *dSo;
+    s = stage(h, {input(&dW, waypoints, (S + B) * 3), input(&dT[0], seg_times, S), output(&dT[1], S),
+                  input(&dED, end_derivs, (size_t)B * 18), output(&dC, coeffs ? S * 24 : 0), output(&dCost, (size_t)B),
+                  output(&dSt, (size_t)B), input(&dSo, so, (size_t)B + 1)});
     if (s != TGMS_OK) return s;
-    char* base = static_cast<char*>(h->d_ws);
-    double* dW = reinterpret_cast<double*>(base + oW);
-    double* dT[2] = {reinterpret_cast<double*>(base + oT0), reinterpret_cast<double*>(base + oT1)};
-    double* dED = end_derivs ? reinterpret_cast<double*>(base + oED) : nullptr;
-    double* dC = reinterpret_cast<double*>(base + oC);
-    double* dCost = reinterpret_cast<double*>(base + oCost);
-    int32_t* dSt = reinterpret_cast<int32_t*>(base + oSt);
-    int32_t* dSo = reinterpret_cast<int32_t*>(base + oSo);
     hipStream_t st = h->stream;
-    TGMS_HIP(h, hipMemcpyAsync(dW, waypoints, nW * 8, hipMemcpyHostToDevice, st));
-    TGMS_HIP(h, hipMemcpyAsync(dT[0], seg_times, S * 8, hipMemcpyHostToDevice, st));
-    if (dED) TGMS_HIP(h, hipMemcpyAsync(dED, end_derivs, nED * 8, hipMemcpyHostToDevice, st));
-    TGMS_HIP(h, hipMemcpyAsync(dSo, so, (size_t)(B + 1) * 4, hipMemcpyHostToDevice, st));
     s = scratch_acquire(h, st);
     if (s == TGMS_OK && plan.uniform_m == 0) s = ensure_perm_device(h, B);
     if (s != TGMS_OK) return s;
     const DevPlanBufs dp{h->d_perm_hist, h->d_perm, h->d_plan};
     int cur = 0;
-    s = refine_loop(h, plan, B, (int64_t)S, dSo, dW, dT, dED, k_T, eta, iters, coeffs ? dC : nullptr, dCost, dSt, st,
-                    &cur, &dp);
-    {  // released on failure too: a band call that launched must still write its marker
-        const tgms_status r_ = scratch_release(h, st);
-        if (s == TGMS_OK) s = r_;
-    }
+    s = scratch_release(h, st, refine_loop(h, plan, B, (int64_t)S, dSo, dW, dT, dED, k_T, eta, iters, dC, dCost, dSt,
+                                           st, &cur, &dp));
     if (s != TGMS_OK) return s;
-    if (coeffs) TGMS_HIP(h, hipMemcpyAsync(coeffs, dC, nC * 8, hipMemcpyDeviceToHost, st));
-    TGMS_HIP(h, hipMemcpyAsync(seg_times, dT[cur], S * 8, hipMemcpyDeviceToHost, st));
-    if (cost) TGMS_HIP(h, hipMemcpyAsync(cost, dCost, (size_t)B * 8, hipMemcpyDeviceToHost, st));
-    std::vector<int32_t> hst;
-    int32_t* stout = status;
-    if (!stout) {
-        hst.resize(B);
-        stout = hst.data();
-    }
-    TGMS_HIP(h, hipMemcpyAsync(stout, dSt, (size_t)B * 4, hipMemcpyDeviceToHost, st));
-    TGMS_HIP(h, hipStreamSynchronize(st));
-    int worst = TGMS_OK;
-    for (int32_t b = 0; b < B; ++b) worst = std::max(worst, (int)stout[b]);
-    return (tgms_status)worst;
+    if (coeffs) TGMS_HIP(h, fetch(h, coeffs, dC, S * 24));
+    TGMS_HIP(h, fetch(h, seg_times, dT[cur], S));
+    if (cost) TGMS_HIP(h, fetch(h, cost, dCost, (size_t)B));
+    return finish_status(h, dSt, status, B, false);  // the worst status, no message
 }
 
 tgms_status tgms_refine_loop_device(tgms_handle* h, int32_t B, const int32_t* h_so, const int32_t* d_so,
                                     const double* dW, double* dT, const double* dED, double k_T, double eta,
                                     int32_t iters, double* dC, double* d_cost, int32_t* dSt, void* stream) {
-    if (!h) return TGMS_ERR_INVALID_ARG;
-    if (h->host) return set_err(h, TGMS_ERR_UNSUPPORTED, "tgms_refine_loop_device needs a GPU handle (tgms_create)");
-    h->last_error.clear();
+    if (tgms_status e = enter(h, __func__); e != TGMS_OK) return e;
     tgms_status s = check_refine_args(h, k_T, eta);
     if (s != TGMS_OK) return s;
     if (iters < 0) return set_err(h, TGMS_ERR_INVALID_ARG, "iters < 0");
@@ -1714,9 +1739,8 @@ tgms_status tgms_refine_loop_device(tgms_handle* h, int32_t B, const int32_t* h_
     s = no_capture(h, st, "tgms_refine_loop_device (it captures and replays its own graph)");
     if (s == TGMS_OK) s = scratch_acquire(h, st);
     if (s != TGMS_OK) return s;
-    s = loop_on_device(h, B, (int64_t)h_so[B], um, d_so, dW, dT, dED, k_T, eta, iters, dC, d_cost, dSt, st);
-    const tgms_status r = scratch_release(h, st);  // on failure too (the band marker)
-    return s != TGMS_OK ? s : r;
+    return scratch_release(h, st, loop_on_device(h, B, (int64_t)h_so[B], um, d_so, dW, dT, dED, k_T, eta, iters, dC,
+                                                 d_cost, dSt, st));
 }
 
 int64_t tgms_sample_count(double total_T, double dt) {
@@ -1745,9 +1769,7 @@ tgms_status tgms_sample_batch_device(tgms_handle* h, int32_t B, const int32_t* d
                                      const double* dW, const double* dT, const double* dED,
                                      const double* dC, double dt, int yaw_mode, double yaw_const,
                                      const int64_t* d_sample_offsets, double* d_out, void* stream) {
-    if (!h) return TGMS_ERR_INVALID_ARG;
-    if (h->host) return set_err(h, TGMS_ERR_UNSUPPORTED, "tgms_sample_batch_device needs a GPU handle (tgms_create)");
-    h->last_error.clear();
+    if (tgms_status e = enter(h, __func__); e != TGMS_OK) return e;
     if (B < 0 || !(dt > 0.0) || (yaw_mode != TGMS_YAW_CONSTANT && yaw_mode != TGMS_YAW_VELOCITY))
         return set_err(h, TGMS_ERR_INVALID_ARG, "bad B, dt or yaw_mode");
     if (B == 0) return TGMS_OK;
@@ -1763,8 +1785,7 @@ tgms_status tgms_sample_batch(tgms_handle* h, int32_t B, const int32_t* so, cons
                               const double* seg_times, const double* end_derivs, const double* coeffs,
                               double dt, int yaw_mode, double yaw_const,
                               const int64_t* sample_offsets, double* out) {
-    if (!h) return TGMS_ERR_INVALID_ARG;
-    h->last_error.clear();
+    if (tgms_status e = enter(h); e != TGMS_OK) return e;
     tgms_status s = check_offsets(h, B, so, TGMS_MAX_SEGMENTS, nullptr, nullptr);
     if (s != TGMS_OK) return s;
     if (B == 0) return TGMS_OK;
@@ -1781,38 +1802,17 @@ tgms_status tgms_sample_batch(tgms_handle* h, int32_t B, const int32_t* so, cons
         }
         return TGMS_OK;
     }
-    TGMS_HIP(h, hipSetDevice(h->device));
-    const size_t S = (size_t)so[B];
-    const size_t nS = (size_t)sample_offsets[B];
-    const size_t nW = (S + B) * 3, nT = S, nED = end_derivs ? (size_t)B * 18 : 0, nC = S * 24;
-    size_t off = 0;
-    const size_t oW = off; off = align256(off + nW * 8);
-    const size_t oT = off; off = align256(off + nT * 8);
-    const size_t oED = off; off = align256(off + nED * 8);
-    const size_t oC = off; off = align256(off + nC * 8);
-    const size_t oSo = off; off = align256(off + (size_t)(B + 1) * 4);
-    const size_t oSmp = off; off = align256(off + (size_t)(B + 1) * 8);
-    const size_t oOut = off; off = align256(off + nS * TGMS_GOAL_STRIDE * 8);
-    s = ensure_ws(h, off);
+    const size_t S = (size_t)so[B], nOut = (size_t)sample_offsets[B] * TGMS_GOAL_STRIDE;
+    double *dW, *dT, *dED, *dC, *dOut;
+    int32_t* dSo;
+    int64_t* dSmp;
+    s = stage(h, {input(&dW, waypoints, (S + B) * 3), input(&dT, seg_times, S), input(&dED, end_derivs, (size_t)B * 18),
+                  input(&dC, coeffs, S * 24), input(&dSo, so, (size_t)B + 1),
+                  input(&dSmp, sample_offsets, (size_t)B + 1), output(&dOut, nOut)});
     if (s != TGMS_OK) return s;
-    char* base = static_cast<char*>(h->d_ws);
-    double* dW = reinterpret_cast<double*>(base + oW);
-    double* dT = reinterpret_cast<double*>(base + oT);
-    double* dED = end_derivs ? reinterpret_cast<double*>(base + oED) : nullptr;
-    double* dC = reinterpret_cast<double*>(base + oC);
-    int32_t* dSo = reinterpret_cast<int32_t*>(base + oSo);
-    int64_t* dSmp = reinterpret_cast<int64_t*>(base + oSmp);
-    double* dOut = reinterpret_cast<double*>(base + oOut);
-    hipStream_t st = h->stream;
-    TGMS_HIP(h, hipMemcpyAsync(dW, waypoints, nW * 8, hipMemcpyHostToDevice, st));
-    TGMS_HIP(h, hipMemcpyAsync(dT, seg_times, nT * 8, hipMemcpyHostToDevice, st));
-    if (dED) TGMS_HIP(h, hipMemcpyAsync(dED, end_derivs, nED * 8, hipMemcpyHostToDevice, st));
-    TGMS_HIP(h, hipMemcpyAsync(dC, coeffs, nC * 8, hipMemcpyHostToDevice, st));
-    TGMS_HIP(h, hipMemcpyAsync(dSo, so, (size_t)(B + 1) * 4, hipMemcpyHostToDevice, st));
-    TGMS_HIP(h, hipMemcpyAsync(dSmp, sample_offsets, (size_t)(B + 1) * 8, hipMemcpyHostToDevice, st));
-    TGMS_HIP(h, tgms::launch_sample(B, dSo, dW, dT, dED, dC, dt, yaw_mode, yaw_const, dSmp, dOut, st));
-    TGMS_HIP(h, hipMemcpyAsync(out, dOut, nS * TGMS_GOAL_STRIDE * 8, hipMemcpyDeviceToHost, st));
-    TGMS_HIP(h, hipStreamSynchronize(st));
+    TGMS_HIP(h, tgms::launch_sample(B, dSo, dW, dT, dED, dC, dt, yaw_mode, yaw_const, dSmp, dOut, h->stream));
+    TGMS_HIP(h, fetch(h, out, dOut, nOut));
+    TGMS_HIP(h, hipStreamSynchronize(h->stream));
     return TGMS_OK;
 }
 
@@ -1836,9 +1836,7 @@ tgms_status tgms_extrema_batch_device(tgms_handle* h, int32_t B, const int32_t* 
                                       const double* dT, const double* dED, const double* dC, double dt,
                                       const tgms_limits* limits, double* d_extrema, int32_t* d_flags,
                                       void* stream) {
-    if (!h) return TGMS_ERR_INVALID_ARG;
-    if (h->host) return set_err(h, TGMS_ERR_UNSUPPORTED, "tgms_extrema_batch_device needs a GPU handle (tgms_create)");
-    h->last_error.clear();
+    if (tgms_status e = enter(h, __func__); e != TGMS_OK) return e;
     if (B < 0 || !(dt > 0.0) || !std::isfinite(dt)) return set_err(h, TGMS_ERR_INVALID_ARG, "bad B or dt");
     tgms_limits lim;
     if (!resolve_limits(limits, &lim)) return set_err(h, TGMS_ERR_INVALID_ARG, "NaN limit or pmin > pmax");
@@ -1854,8 +1852,7 @@ tgms_status tgms_extrema_batch_device(tgms_handle* h, int32_t B, const int32_t* 
 tgms_status tgms_extrema_batch(tgms_handle* h, int32_t B, const int32_t* so, const double* waypoints,
                                const double* seg_times, const double* end_derivs, const double* coeffs, double dt,
                                const tgms_limits* limits, double* extrema, int32_t* flags) {
-    if (!h) return TGMS_ERR_INVALID_ARG;
-    h->last_error.clear();
+    if (tgms_status e = enter(h); e != TGMS_OK) return e;
     tgms_status s = check_offsets(h, B, so, TGMS_MAX_SEGMENTS, nullptr, nullptr);
     if (s != TGMS_OK) return s;
     if (!(dt > 0.0) || !std::isfinite(dt)) return set_err(h, TGMS_ERR_INVALID_ARG, "bad dt");
@@ -1876,48 +1873,15 @@ tgms_status tgms_extrema_batch(tgms_handle* h, int32_t B, const int32_t* so, con
         }
         return TGMS_OK;
     }
-    TGMS_HIP(h, hipSetDevice(h->device));
     const size_t S = (size_t)so[B];
-    const size_t nW = (S + B) * 3, nT = S, nED = end_derivs ? (size_t)B * 18 : 0, nC = S * 24;
-    size_t off = 0;
-    const size_t oW = off; off = align256(off + nW * 8);
-    const size_t oT = off; off = align256(off + nT * 8);
-    const size_t oED = off; off = align256(off + nED * 8);
-    const size_t oC = off; off = align256(off + nC * 8);
-    const size_t oSo = off; off = align256(off + (size_t)(B + 1) * 4);
-    // both results in one region, the flags right behind the records: one download
-    const size_t nExt = (size_t)B * TGMS_EXTREMA_STRIDE * 8, nFl = (size_t)B * 4;
-    const size_t oExt = off; off = align256(off + nExt + nFl);
-    const size_t oFl = oExt + nExt;
-    s = ensure_ws(h, off);
+    double *dW, *dT, *dED, *dC;
+    int32_t* dSo;
+    ResultPair res{extrema, flags, (size_t)B * TGMS_EXTREMA_STRIDE, (size_t)B};  // 80 B + 4 B per trajectory
+    s = stage(h, {input(&dW, waypoints, (S + B) * 3), input(&dT, seg_times, S), input(&dED, end_derivs, (size_t)B * 18),
+                  input(&dC, coeffs, S * 24), input(&dSo, so, (size_t)B + 1), output(&res)});
     if (s != TGMS_OK) return s;
-    char* base = static_cast<char*>(h->d_ws);
-    double* dW = reinterpret_cast<double*>(base + oW);
-    double* dT = reinterpret_cast<double*>(base + oT);
-    double* dED = end_derivs ? reinterpret_cast<double*>(base + oED) : nullptr;
-    double* dC = reinterpret_cast<double*>(base + oC);
-    int32_t* dSo = reinterpret_cast<int32_t*>(base + oSo);
-    double* dExt = extrema ? reinterpret_cast<double*>(base + oExt) : nullptr;
-    int32_t* dFl = flags ? reinterpret_cast<int32_t*>(base + oFl) : nullptr;
-    hipStream_t st = h->stream;
-    TGMS_HIP(h, hipMemcpyAsync(dW, waypoints, nW * 8, hipMemcpyHostToDevice, st));
-    TGMS_HIP(h, hipMemcpyAsync(dT, seg_times, nT * 8, hipMemcpyHostToDevice, st));
-    if (dED) TGMS_HIP(h, hipMemcpyAsync(dED, end_derivs, nED * 8, hipMemcpyHostToDevice, st));
-    TGMS_HIP(h, hipMemcpyAsync(dC, coeffs, nC * 8, hipMemcpyHostToDevice, st));
-    TGMS_HIP(h, hipMemcpyAsync(dSo, so, (size_t)(B + 1) * 4, hipMemcpyHostToDevice, st));
-    TGMS_HIP(h, tgms::launch_extrema(B, dSo, dW, dT, dED, dC, dt, lim, dExt, dFl, st));
-    if (dExt && dFl) {  // 80 B + 4 B per trajectory in one copy, split on the host
-        std::vector<char> res(nExt + nFl);
-        TGMS_HIP(h, hipMemcpyAsync(res.data(), base + oExt, nExt + nFl, hipMemcpyDeviceToHost, st));
-        TGMS_HIP(h, hipStreamSynchronize(st));
-        std::memcpy(extrema, res.data(), nExt);
-        std::memcpy(flags, res.data() + nExt, nFl);
-        return TGMS_OK;
-    }
-    if (dExt) TGMS_HIP(h, hipMemcpyAsync(extrema, dExt, nExt, hipMemcpyDeviceToHost, st));
-    if (dFl) TGMS_HIP(h, hipMemcpyAsync(flags, dFl, nFl, hipMemcpyDeviceToHost, st));
-    TGMS_HIP(h, hipStreamSynchronize(st));
-    return TGMS_OK;
+    TGMS_HIP(h, tgms::launch_extrema(B, dSo, dW, dT, dED, dC, dt, lim, res.d_rec(), res.d_flags(), h->stream));
+    return download(h, res);
 }
 
 // ---- continuous feasibility bounds: the same record and flags, no dt ----
@@ -1925,9 +1889,7 @@ tgms_status tgms_extrema_batch(tgms_handle* h, int32_t B, const int32_t* so, con
 tgms_status tgms_bounds_batch_device(tgms_handle* h, int32_t B, const int32_t* d_so, const double* dT,
                                      const double* dC, const tgms_limits* limits, double* d_extrema,
                                      int32_t* d_flags, void* stream) {
-    if (!h) return TGMS_ERR_INVALID_ARG;
-    if (h->host) return set_err(h, TGMS_ERR_UNSUPPORTED, "tgms_bounds_batch_device needs a GPU handle (tgms_create)");
-    h->last_error.clear();
+    if (tgms_status e = enter(h, __func__); e != TGMS_OK) return e;
     if (B < 0) return set_err(h, TGMS_ERR_INVALID_ARG, "bad B");
     tgms_limits lim;
     if (!resolve_limits(limits, &lim)) return set_err(h, TGMS_ERR_INVALID_ARG, "NaN limit or pmin > pmax");
@@ -1941,8 +1903,7 @@ tgms_status tgms_bounds_batch_device(tgms_handle* h, int32_t B, const int32_t* d
 
 tgms_status tgms_bounds_batch(tgms_handle* h, int32_t B, const int32_t* so, const double* seg_times,
                               const double* coeffs, const tgms_limits* limits, double* extrema, int32_t* flags) {
-    if (!h) return TGMS_ERR_INVALID_ARG;
-    h->last_error.clear();
+    if (tgms_status e = enter(h); e != TGMS_OK) return e;
     tgms_status s = check_offsets(h, B, so, TGMS_MAX_SEGMENTS, nullptr, nullptr);
     if (s != TGMS_OK) return s;
     tgms_limits lim;
@@ -1960,42 +1921,14 @@ tgms_status tgms_bounds_batch(tgms_handle* h, int32_t B, const int32_t* so, cons
         }
         return TGMS_OK;
     }
-    TGMS_HIP(h, hipSetDevice(h->device));
     const size_t S = (size_t)so[B];
-    const size_t nT = S, nC = S * 24;
-    size_t off = 0;
-    const size_t oT = off; off = align256(off + nT * 8);
-    const size_t oC = off; off = align256(off + nC * 8);
-    const size_t oSo = off; off = align256(off + (size_t)(B + 1) * 4);
-    // both results in one region, the flags right behind the records: one download
-    const size_t nExt = (size_t)B * TGMS_EXTREMA_STRIDE * 8, nFl = (size_t)B * 4;
-    const size_t oExt = off; off = align256(off + nExt + nFl);
-    const size_t oFl = oExt + nExt;
-    s = ensure_ws(h, off);
+    double *dT, *dC;
+    int32_t* dSo;
+    ResultPair res{extrema, flags, (size_t)B * TGMS_EXTREMA_STRIDE, (size_t)B};  // 80 B + 4 B per trajectory
+    s = stage(h, {input(&dT, seg_times, S), input(&dC, coeffs, S * 24), input(&dSo, so, (size_t)B + 1), output(&res)});
     if (s != TGMS_OK) return s;
-    char* base = static_cast<char*>(h->d_ws);
-    double* dT = reinterpret_cast<double*>(base + oT);
-    double* dC = reinterpret_cast<double*>(base + oC);
-    int32_t* dSo = reinterpret_cast<int32_t*>(base + oSo);
-    double* dExt = extrema ? reinterpret_cast<double*>(base + oExt) : nullptr;
-    int32_t* dFl = flags ? reinterpret_cast<int32_t*>(base + oFl) : nullptr;
-    hipStream_t st = h->stream;
-    TGMS_HIP(h, hipMemcpyAsync(dT, seg_times, nT * 8, hipMemcpyHostToDevice, st));
-    TGMS_HIP(h, hipMemcpyAsync(dC, coeffs, nC * 8, hipMemcpyHostToDevice, st));
-    TGMS_HIP(h, hipMemcpyAsync(dSo, so, (size_t)(B + 1) * 4, hipMemcpyHostToDevice, st));
-    TGMS_HIP(h, tgms::launch_bounds(B, dSo, dT, dC, lim, dExt, dFl, st));
-    if (dExt && dFl) {  // 80 B + 4 B per trajectory in one copy, split on the host
-        std::vector<char> res(nExt + nFl);
-        TGMS_HIP(h, hipMemcpyAsync(res.data(), base + oExt, nExt + nFl, hipMemcpyDeviceToHost, st));
-        TGMS_HIP(h, hipStreamSynchronize(st));
-        std::memcpy(extrema, res.data(), nExt);
-        std::memcpy(flags, res.data() + nExt, nFl);
-        return TGMS_OK;
-    }
-    if (dExt) TGMS_HIP(h, hipMemcpyAsync(extrema, dExt, nExt, hipMemcpyDeviceToHost, st));
-    if (dFl) TGMS_HIP(h, hipMemcpyAsync(flags, dFl, nFl, hipMemcpyDeviceToHost, st));
-    TGMS_HIP(h, hipStreamSynchronize(st));
-    return TGMS_OK;
+    TGMS_HIP(h, tgms::launch_bounds(B, dSo, dT, dC, lim, res.d_rec(), res.d_flags(), h->stream));
+    return download(h, res);
 }
 
 // ---- continuous swarm separation: closest approach of trajectory pairs ----
@@ -2025,10 +1958,7 @@ tgms_status tgms_separation_batch_device(tgms_handle* h, int32_t B, const int32_
                                          const double* dC, const double* d_start_times, int64_t P,
                                          const int32_t* d_pairs, const double* scale, double r_min, double* d_sep,
                                          int32_t* d_flags, void* stream) {
-    if (!h) return TGMS_ERR_INVALID_ARG;
-    if (h->host)
-        return set_err(h, TGMS_ERR_UNSUPPORTED, "tgms_separation_batch_device needs a GPU handle (tgms_create)");
-    h->last_error.clear();
+    if (tgms_status e = enter(h, __func__); e != TGMS_OK) return e;
     double sc[3];
     const tgms_status s = check_separation(h, B, P, d_pairs, scale, r_min, d_sep, d_flags, sc);
     if (s != TGMS_OK) return s;
@@ -2043,8 +1973,7 @@ tgms_status tgms_separation_batch_device(tgms_handle* h, int32_t B, const int32_
 tgms_status tgms_separation_batch(tgms_handle* h, int32_t B, const int32_t* so, const double* seg_times,
                                   const double* coeffs, const double* start_times, int64_t P, const int32_t* pairs,
                                   const double* scale, double r_min, double* sep, int32_t* flags) {
-    if (!h) return TGMS_ERR_INVALID_ARG;
-    h->last_error.clear();
+    if (tgms_status e = enter(h); e != TGMS_OK) return e;
     tgms_status s = check_offsets(h, B, so, TGMS_MAX_SEGMENTS, nullptr, nullptr);
     if (s != TGMS_OK) return s;
     double sc[3];
@@ -2078,48 +2007,15 @@ tgms_status tgms_separation_batch(tgms_handle* h, int32_t B, const int32_t* so, 
         }
         return TGMS_OK;
     }
-    TGMS_HIP(h, hipSetDevice(h->device));
     const size_t S = (size_t)so[B];
-    const size_t nT = S, nC = S * 24, nT0 = start_times ? (size_t)B : 0, nP = pairs ? (size_t)P * 2 : 0;
-    size_t off = 0;
-    const size_t oT = off; off = align256(off + nT * 8);
-    const size_t oC = off; off = align256(off + nC * 8);
-    const size_t oT0 = off; off = align256(off + nT0 * 8);
-    const size_t oSo = off; off = align256(off + (size_t)(B + 1) * 4);
-    const size_t oP = off; off = align256(off + nP * 4);
-    // both results in one region, the flags right behind the records: one download
-    const size_t nSep = (size_t)P * TGMS_SEP_STRIDE * 8, nFl = (size_t)P * 4;
-    const size_t oSep = off; off = align256(off + nSep + nFl);
-    const size_t oFl = oSep + nSep;
-    s = ensure_ws(h, off);
+    double *dT, *dC, *dT0;
+    int32_t *dSo, *dP;
+    ResultPair res{sep, flags, (size_t)P * TGMS_SEP_STRIDE, (size_t)P};  // 16 B + 4 B per pair
+    s = stage(h, {input(&dT, seg_times, S), input(&dC, coeffs, S * 24), input(&dT0, start_times, (size_t)B),
+                  input(&dSo, so, (size_t)B + 1), input(&dP, pairs, (size_t)P * 2), output(&res)});
     if (s != TGMS_OK) return s;
-    char* base = static_cast<char*>(h->d_ws);
-    double* dT = reinterpret_cast<double*>(base + oT);
-    double* dC = reinterpret_cast<double*>(base + oC);
-    double* dT0 = start_times ? reinterpret_cast<double*>(base + oT0) : nullptr;
-    int32_t* dSo = reinterpret_cast<int32_t*>(base + oSo);
-    int32_t* dP = pairs ? reinterpret_cast<int32_t*>(base + oP) : nullptr;
-    double* dSep = sep ? reinterpret_cast<double*>(base + oSep) : nullptr;
-    int32_t* dFl = flags ? reinterpret_cast<int32_t*>(base + oFl) : nullptr;
-    hipStream_t st = h->stream;
-    TGMS_HIP(h, hipMemcpyAsync(dT, seg_times, nT * 8, hipMemcpyHostToDevice, st));
-    TGMS_HIP(h, hipMemcpyAsync(dC, coeffs, nC * 8, hipMemcpyHostToDevice, st));
-    if (dT0) TGMS_HIP(h, hipMemcpyAsync(dT0, start_times, nT0 * 8, hipMemcpyHostToDevice, st));
-    TGMS_HIP(h, hipMemcpyAsync(dSo, so, (size_t)(B + 1) * 4, hipMemcpyHostToDevice, st));
-    if (dP) TGMS_HIP(h, hipMemcpyAsync(dP, pairs, nP * 4, hipMemcpyHostToDevice, st));
-    TGMS_HIP(h, tgms::launch_separation(B, dSo, dT, dC, dT0, P, dP, sc, r_min, dSep, dFl, st));
-    if (dSep && dFl) {  // 16 B + 4 B per pair in one copy, split on the host
-        std::vector<char> res(nSep + nFl);
-        TGMS_HIP(h, hipMemcpyAsync(res.data(), base + oSep, nSep + nFl, hipMemcpyDeviceToHost, st));
-        TGMS_HIP(h, hipStreamSynchronize(st));
-        std::memcpy(sep, res.data(), nSep);
-        std::memcpy(flags, res.data() + nSep, nFl);
-        return TGMS_OK;
-    }
-    if (dSep) TGMS_HIP(h, hipMemcpyAsync(sep, dSep, nSep, hipMemcpyDeviceToHost, st));
-    if (dFl) TGMS_HIP(h, hipMemcpyAsync(flags, dFl, nFl, hipMemcpyDeviceToHost, st));
-    TGMS_HIP(h, hipStreamSynchronize(st));
-    return TGMS_OK;
+    TGMS_HIP(h, tgms::launch_separation(B, dSo, dT, dC, dT0, P, dP, sc, r_min, res.d_rec(), res.d_flags(), h->stream));
+    return download(h, res);
 }
 
 // ---- multi-GPU ----
@@ -2230,10 +2126,8 @@ tgms_status tgms_multi_schedule(int32_t device_count, int32_t B, const int32_t* 
 tgms_status tgms_solve_batch_multi_device(tgms_handle* h, int32_t B, const int32_t* h_so, const int32_t* d_so,
                                           const double* dW, const double* dT, const double* dED, double* dC,
                                           int32_t* dSt, void* stream) {
-    if (!h) return TGMS_ERR_INVALID_ARG;
-    if (h->host) return set_err(h, TGMS_ERR_UNSUPPORTED, "tgms_solve_batch_multi_device needs a GPU handle (tgms_create)");
+    if (tgms_status e = enter(h, __func__); e != TGMS_OK) return e;
     if (!h->multi) return tgms_solve_batch_device(h, B, h_so, d_so, dW, dT, dED, dC, dSt, stream);
-    h->last_error.clear();
     Plan checked;
     // reduced method: no pass over a ragged batch's offsets on the host (its devices group and
     // check it, include/tgms.h); band / dense: the host-planned pieces need the validated counts
@@ -2262,14 +2156,12 @@ tgms_status tgms_solve_batch_multi_device(tgms_handle* h, int32_t B, const int32
 tgms_status tgms_refine_loop_multi_device(tgms_handle* h, int32_t B, const int32_t* h_so, const int32_t* d_so,
                                           const double* dW, double* dT, const double* dED, double k_T, double eta,
                                           int32_t iters, double* dC, double* d_cost, int32_t* dSt, void* stream) {
-    if (!h) return TGMS_ERR_INVALID_ARG;
-    if (h->host) return set_err(h, TGMS_ERR_UNSUPPORTED, "tgms_refine_loop_multi_device needs a GPU handle (tgms_create)");
+    if (tgms_status e = enter(h, __func__); e != TGMS_OK) return e;
     // one device and no self-gather: the whole batch is device 0's shard, solved in place,
     // so the single-device loop (its captured graph, the M grouping on the device) is that
     // shard's path
     if (!h->multi || (h->multi->n == 1 && !h->multi->self_gather))
         return tgms_refine_loop_device(h, B, h_so, d_so, dW, dT, dED, k_T, eta, iters, dC, d_cost, dSt, stream);
-    h->last_error.clear();
     tgms_status s = check_refine_args(h, k_T, eta);
     if (s != TGMS_OK) return s;
     if (iters < 0) return set_err(h, TGMS_ERR_INVALID_ARG, "iters < 0");
@@ -2311,39 +2203,19 @@ tgms_status tgms_refine_loop_multi_device(tgms_handle* h, int32_t B, const int32
 tgms_status tgms_solve_batch_multi(tgms_handle* h, int32_t B, const int32_t* so, const double* waypoints,
                                    const double* seg_times, const double* end_derivs, double* coeffs,
                                    int32_t* status) {
-    if (!h) return TGMS_ERR_INVALID_ARG;
-    if (h->host) return set_err(h, TGMS_ERR_UNSUPPORTED, "tgms_solve_batch_multi needs a GPU handle (tgms_create)");
+    if (tgms_status e = enter(h, __func__); e != TGMS_OK) return e;
     if (!h->multi) return tgms_solve_batch(h, B, so, waypoints, seg_times, end_derivs, coeffs, status);
-    h->last_error.clear();
     Plan checked;
     tgms_status s = check_offsets(h, B, so, max_m_for(h), &checked.counts, &checked.uniform_m);
     if (s != TGMS_OK || B == 0) return s;
     if (!waypoints || !seg_times || !coeffs)
         return set_err(h, TGMS_ERR_INVALID_ARG, "NULL waypoints/seg_times/coeffs");
-    TGMS_HIP(h, hipSetDevice(h->device));
     const size_t S = (size_t)so[B];
-    const size_t nW = (S + B) * 3, nT = S, nED = end_derivs ? (size_t)B * 18 : 0, nC = S * 24;
-    size_t off = 0;
-    const size_t oW = off; off = align256(off + nW * 8);
-    const size_t oT = off; off = align256(off + nT * 8);
-    const size_t oED = off; off = align256(off + nED * 8);
-    const size_t oC = off; off = align256(off + nC * 8);
-    const size_t oSt = off; off = align256(off + (size_t)B * 4);
-    const size_t oSo = off; off = align256(off + (size_t)(B + 1) * 4);
-    s = ensure_ws(h, off);
+    double *dW, *dT, *dED, *dC;
+    int32_t *dSt, *dSo;
+    s = stage(h, {input(&dW, waypoints, (S + B) * 3), input(&dT, seg_times, S), input(&dED, end_derivs, (size_t)B * 18),
+                  output(&dC, S * 24), output(&dSt, (size_t)B), input(&dSo, so, (size_t)B + 1)});
     if (s != TGMS_OK) return s;
-    char* base = static_cast<char*>(h->d_ws);
-    double* dW = reinterpret_cast<double*>(base + oW);
-    double* dT = reinterpret_cast<double*>(base + oT);
-    double* dED = end_derivs ? reinterpret_cast<double*>(base + oED) : nullptr;
-    double* dC = reinterpret_cast<double*>(base + oC);
-    int32_t* dSt = reinterpret_cast<int32_t*>(base + oSt);
-    int32_t* dSo = reinterpret_cast<int32_t*>(base + oSo);
-    hipStream_t st = h->stream;
-    TGMS_HIP(h, hipMemcpyAsync(dW, waypoints, nW * 8, hipMemcpyHostToDevice, st));
-    TGMS_HIP(h, hipMemcpyAsync(dT, seg_times, nT * 8, hipMemcpyHostToDevice, st));
-    if (dED) TGMS_HIP(h, hipMemcpyAsync(dED, end_derivs, nED * 8, hipMemcpyHostToDevice, st));
-    TGMS_HIP(h, hipMemcpyAsync(dSo, so, (size_t)(B + 1) * 4, hipMemcpyHostToDevice, st));
     MultiArgs a;
     a.checked = &checked;
     a.B = B;
@@ -2354,19 +2226,11 @@ tgms_status tgms_solve_batch_multi(tgms_handle* h, int32_t B, const int32_t* so,
     a.dED = dED;
     a.dC = dC;
     a.dSt = dSt;
-    s = multi_run(h, a, st);
+    s = multi_run(h, a, h->stream);
     (void)hipSetDevice(h->device);
     if (s != TGMS_OK) return s;
-    TGMS_HIP(h, hipMemcpyAsync(coeffs, dC, nC * 8, hipMemcpyDeviceToHost, st));
-    std::vector<int32_t> hst;
-    int32_t* stout = status;
-    if (!stout) {
-        hst.resize(B);
-        stout = hst.data();
-    }
-    TGMS_HIP(h, hipMemcpyAsync(stout, dSt, (size_t)B * 4, hipMemcpyDeviceToHost, st));
-    TGMS_HIP(h, hipStreamSynchronize(st));
-    return worst_status(h, stout, B);
+    TGMS_HIP(h, fetch(h, coeffs, dC, S * 24));
+    return finish_status(h, dSt, status, B, true);
 }
 
 }  // extern "C"
