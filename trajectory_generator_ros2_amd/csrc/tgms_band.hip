@@ -269,18 +269,8 @@ __device__ __forceinline__ double row_entry(int q, int pat_off, int rsrc, const 
 typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
 typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 
-// Row positions: in registers (default, 10 VGPRs) or in the trajectory's LDS block.
-#ifndef TGMS_BAND_POS_LDS
-#define TGMS_BAND_POS_LDS 0
-#endif
-#if TGMS_BAND_POS_LDS
-typedef int* PosRef;
-#else
-typedef int (&PosRef)[WR];
-#endif
-
 template <int M, bool HAS_ED, int R>
-__device__ __forceinline__ void quad_step(const int k, const int q0, double (&u)[WR][NJ], PosRef P,
+__device__ __forceinline__ void quad_step(const int k, const int q0, double (&u)[WR][NJ], int (&pos)[WR],
                                           int& sing, __amdgpu_buffer_rsrc_t rs, const uint32_t vrow,
                                           const int* sd, double* X) {
     constexpr int N = 14 * M + 2;
@@ -294,20 +284,9 @@ __device__ __forceinline__ void quad_step(const int k, const int q0, double (&u)
     double m = fabs(u[0][JR]);
 #pragma unroll
     for (int r = 1; r < WR; ++r) m = fmax(m, fabs(u[r][JR]));
-    // row positions from the trajectory's LDS block (registers are the scarce resource at
-    // two wavefronts per SIMD; the quad's lanes read the same words)
-#if TGMS_BAND_POS_LDS
-    int pos[WR];
-    {
-        const int4 pa = *reinterpret_cast<const int4*>(P), pb = *reinterpret_cast<const int4*>(P + 4);
-        const int2 pc = *reinterpret_cast<const int2*>(P + 8);
-        pos[0] = pa.x; pos[1] = pa.y; pos[2] = pa.z; pos[3] = pa.w;
-        pos[4] = pb.x; pos[5] = pb.y; pos[6] = pb.z; pos[7] = pb.w;
-        pos[8] = pc.x; pos[9] = pc.y;
-    }
-#else
-    int(&pos)[WR] = P;
-#endif
+    // (the row positions pos[] live in registers, 10 VGPRs; a variant with them in the
+    // trajectory's LDS block was one probe of round 5's store hazard and changed nothing,
+    // profiles/r05_band_lane_variants.jsonl)
     int key = 0x7fffffff, rk = 0;  // rk: the row at position k
 #pragma unroll
     for (int r = 0; r < WR; ++r) {
@@ -416,17 +395,12 @@ __device__ __forceinline__ void quad_step(const int k, const int q0, double (&u)
     }
     // interchange: the row at position k takes the pivot's position; the pivot's slot
     // holds row k + 10 now (the second store wins when the pivot is the row at position k)
-#if TGMS_BAND_POS_LDS
-    P[rk] = cp;
-    P[ps] = re;
-#else
 #pragma unroll
     for (int r = 0; r < WR; ++r) {
         int v = pos[r];
         v = (v == k) ? cp : v;
         pos[r] = (ps == r) ? re : v;
     }
-#endif
 }
 
 // Back substitution, eight lanes per trajectory, slot order.  Lane l holds slots l, l+8,
@@ -508,7 +482,6 @@ __global__ __launch_bounds__(QW * W64) __attribute__((amdgpu_waves_per_eu(TGMS_B
     constexpr int XL = x_len(M);
     __shared__ int s_desc[NPAT * WC];                  // pattern table of the interleaved KKT
     __shared__ double s_x[QW][QTW][XL];                // per-trajectory Vc | T | W | ED
-    __shared__ alignas(16) int s_pos[QW][QTW][12];     // per-trajectory row positions (10 used)
 
     for (int n = threadIdx.x; n < NPAT * WC; n += QW * W64) {
         const int pat = n / WC, d = n % WC - KL;
@@ -575,11 +548,7 @@ __global__ __launch_bounds__(QW * W64) __attribute__((amdgpu_waves_per_eu(TGMS_B
 
         // ---- the initial window: rows 0..9 over columns 0..18 (slot s = column s)
         double u[WR][NJ];
-#if TGMS_BAND_POS_LDS
-        int* const P = &s_pos[0][0][0] + (wv * QTW + g) * 12;
-#else
-        int P[WR];
-#endif
+        int P[WR];  // row positions
 #define IROW(RR)                                                                      \
     {                                                                                 \
         int pat_off, rsrc, seg;                                                       \

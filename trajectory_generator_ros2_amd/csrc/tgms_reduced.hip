@@ -34,15 +34,14 @@
 namespace tgms {
 namespace {
 
+// Every supported segment count: the switches from a runtime M to a template argument.
+#define TGMS_CASES(X) X(1) X(2) X(3) X(4) X(5) X(6) X(7) X(8) X(9) X(10) X(11) X(12) X(13) X(14) X(15) X(16)
 // Waves per SIMD the register allocation must allow: two for the axis-sequential
 // solve while its state fits 256 registers without spilling (M <= 11), else one.
 #define TGMS_WAVES(M) ((M) <= TGMS_TWO_WAVE_MAX_M ? 2 : 1)
-// The refinement loop's one-wave class as persistent waves sized from the plan (round 6,
+// The refinement loop's one-wave class runs as persistent waves sized from the plan (round 6,
 // k_refine_loop_dev); TGMS_C5_W1: SIMD time per unit of work of a one-wave tile against a
 // two-wave tile (x 100), TGMS_C5_BIAS: the share's bias (%)
-#ifndef TGMS_C5_PERSIST
-#define TGMS_C5_PERSIST 1
-#endif
 #ifndef TGMS_C5_W1
 #define TGMS_C5_W1 157
 #endif
@@ -50,26 +49,13 @@ namespace {
 #define TGMS_C5_BIAS 110
 #endif
 // One-wave-per-SIMD kernels solve the three axes side by side (pair_solve_joint).
-// The axis-sequential lane-pair solve reads the next knot's waypoints and 1/T from the
-// LDS stage one step ahead (the per-step SCHED_FENCE otherwise exposes the LDS latency at
-// every step): config 5 0.477-0.488 -> 0.462-0.473 ms, uniform M = 3/5 -2-3 % (round 4).
-// The joint solve does the same (TGMS_JOINT_PREFETCH): the one-wave class timed alone
-// 0.232-0.233 -> 0.216-0.220 ms, the whole config-5 call 0.486-0.492 -> 0.477-0.485 ms,
-// three alternating runs (round 5, profiles/r05_c5_joint_prefetch_ab.jsonl).
-#ifndef TGMS_PAIR_PREFETCH
-#define TGMS_PAIR_PREFETCH 1
-#endif
-#ifndef TGMS_JOINT_PREFETCH
-#define TGMS_JOINT_PREFETCH 1
-#endif
-#ifndef TGMS_JOINT_AXES
-#define TGMS_JOINT_AXES 1
-#endif
-// The refinement gradient in the Legendre basis of the snap (seg_grad_u, round 6); 0: round
-// 5's P4..P7 + seg_cost_p form (A/B builds).
-#ifndef TGMS_GRAD_LEGENDRE
-#define TGMS_GRAD_LEGENDRE 1
-#endif
+// Both lane-pair solves read the next knot's waypoints and 1/T from the LDS stage one step
+// ahead (the per-step SCHED_FENCE otherwise exposes the LDS latency at every step).  Reading
+// in step was the other arm of an A/B: axis-sequential solve, config 5 0.477-0.488 ->
+// 0.462-0.473 ms (round 4, profiles/r04_c5_pair_prefetch_ab.jsonl); joint solve, one-wave
+// class alone 0.232-0.233 -> 0.216-0.220 ms (round 5, profiles/r05_c5_joint_prefetch_ab.jsonl).
+// The refinement gradient is taken in the Legendre basis of the snap (seg_grad_u, round 6);
+// round 5's P4..P7 form measured slower (profiles/r06_c5_legendre_ab.jsonl).
 
 // Scheduling fence between unrolled chain / emission steps.  The compiler-level
 // memory clobber also stops CSE of LDS reads across steps: re-reading LDS is far
@@ -111,44 +97,17 @@ constexpr int PSTRIDE = 33;  // LDS row stride (doubles) of the [field][trajecto
 constexpr int OSTRIDE = 10;
 
 // The one-wave (joint-axes, M > TGMS_TWO_WAVE_MAX_M) kernels read the stage with no second
-// wavefront to hide LDS time, and with the padded stride the two lanes of a pair collide:
-// a ds_read_b64 serves lanes 0-31 and 32-63 in one LDS cycle each, i.e. 16 trajectories
-// whose even lanes read knot j and odd lanes knot M-j, two 32-bank windows at a distance
-// of 2 (F_e - F_o) banks that overlap for almost every j (PMC of the one-wave class alone:
-// SQ_LDS_BANK_CONFLICT 2.1x SQ_ACTIVE_INST_LDS).  Swizzled: rows of exactly 32 doubles, and
-// the rows of the second half of the trajectory (knot k with 2k > M, segment i with
-// 2i + 1 > M) hold trajectory t at column t ^ 16, so in every read the pair's two lanes
-// land in opposite bank halves (the middle knot / segment both read is one address).
-// Measured (round 5, profiles/r05_c5_swizzle_ab.jsonl): the conflict cycles of the one-wave
-// class halve (4.23 M -> 2.15 M per call) but its time does not move (0.213-0.216 ms both
-// ways; the whole call 0.481-0.488 vs 0.482-0.493 ms; for every M, where the two-wave
-// class spills 2 VGPRs, 0.480-0.490), so it is off.
-#ifndef TGMS_PAIR_SWIZZLE
-#define TGMS_PAIR_SWIZZLE 0
-#endif
-#ifndef TGMS_PAIR_SWIZZLE_MIN_M
-#define TGMS_PAIR_SWIZZLE_MIN_M (TGMS_TWO_WAVE_MAX_M + 1)
-#endif
-template <int M>
-constexpr bool pair_swz() { return TGMS_PAIR_SWIZZLE && M >= TGMS_PAIR_SWIZZLE_MIN_M; }
-template <int M>
-constexpr int pstride() { return pair_swz<M>() ? TPW : PSTRIDE; }
-template <int M>
-__device__ __forceinline__ int w_at(int q, int t) {  // field q = 3 knot + axis, trajectory t
-    if constexpr (pair_swz<M>()) return q * TPW + ((2 * (q / 3) > M) ? (t ^ 16) : t);
-    else return q * PSTRIDE + t;
-}
-template <int M>
-__device__ __forceinline__ int r_at(int i, int t) {  // segment i, trajectory t
-    if constexpr (pair_swz<M>()) return i * TPW + ((2 * i + 1 > M) ? (t ^ 16) : t);
-    else return i * PSTRIDE + t;
-}
+// wavefront to hide LDS time, and with the padded stride the two lanes of a pair collide
+// (PMC of the one-wave class alone: SQ_LDS_BANK_CONFLICT 2.1x SQ_ACTIVE_INST_LDS).  A swizzled
+// layout (32-double rows, the far half's columns at t ^ 16) halved the conflict cycles but
+// the class's time did not move (round 5, profiles/r05_c5_swizzle_ab.jsonl), so the plain
+// padded layout stays.
 
 // One group's staged inputs, [field][trajectory] with a padded trajectory stride.
 template <int M>
 struct In {
-    double W[(M + 1) * 3 * pstride<M>()];
-    double R[M * pstride<M>()];  // 1/T, computed once while staging (T itself is not staged:
+    double W[(M + 1) * 3 * PSTRIDE];
+    double R[M * PSTRIDE];  // 1/T, computed once while staging (T itself is not staged:
                             // at 2.9 KB for M = 11 it cost the 2-wave kernels their 8th wave per CU)
     int64_t base[TPW];      // coefficient offset (doubles) of each slot's trajectory
     int bad[TPW];
@@ -167,10 +126,14 @@ static_assert(OSTRIDE % 2 == 0, "staged rows must keep 16-B alignment");
 // Per-lane view of the staged inputs in the lane's VIRTUAL frame: the even lane
 // sees the trajectory as is, the odd lane time-reversed (virtual knot j = physical
 // knot M-j, virtual segment i = physical segment M-1-i).
+// The near half (2j < M), the far half and the middle each have their own base pointer.
+// All three hold the same address: the swizzled layout, which needed them apart, is gone,
+// but one pointer in their place changes the compiled kernels (instruction order and
+// address arithmetic in most of them), so merging them waits for a change that re-measures.
 struct LaneView {
     const double* Wb;  // &W[phys knot of virtual knot 0][axis 0][slot] for virtual knots 2j < M
     const double* Wf;  // the same for 2j > M and
-    const double* Wm;  // 2j == M (all three equal unless the stage is swizzled)
+    const double* Wm;  // 2j == M
     const double* Rb;  // &R[...], virtual segments 2i + 1 < M,
     const double* Rf;  // > M and
     const double* Rm;  // == M
@@ -190,19 +153,12 @@ struct LaneView {
 
 template <int M>
 __device__ __forceinline__ LaneView make_view(const In<M>& sm, int slot, bool right) {
-    constexpr int S = pstride<M>();
+    constexpr int S = PSTRIDE;
     LaneView L;
     const double* w0 = sm.W + (right ? M * 3 * S : 0);
     const double* r0 = sm.R + (right ? (M - 1) * S : 0);
-    // swizzled: the even lane's near half (virtual = physical) is unswizzled, its far half
-    // swizzled; the odd lane (virtual knot j = physical M - j) the other way round
-    const int sx = pair_swz<M>() ? (slot ^ 16) : slot;
-    L.Wb = w0 + (right ? sx : slot);
-    L.Wf = w0 + (right ? slot : sx);
-    L.Wm = w0 + slot;
-    L.Rb = r0 + (right ? sx : slot);
-    L.Rf = r0 + (right ? slot : sx);
-    L.Rm = r0 + slot;
+    L.Wb = L.Wf = L.Wm = w0 + slot;
+    L.Rb = L.Rf = L.Rm = r0 + slot;
     L.kstep = right ? -3 * S : 3 * S;
     L.sstep = right ? -S : S;
     L.astep = S;
@@ -398,26 +354,15 @@ __device__ __forceinline__ int out_step(const OutCtx&, int e) { return e; }
 // numbers q_k = HNK_k r_i^(5-k): 5 multiplies per coupling instead of 9 (the signs fold into
 // the consuming FMAs), integer constants throughout.  Factorisation, substitutions and the
 // interface keep their form; the emission and the gradient fold 21 and 3 into their
-// constants, and the given end derivatives are scaled once on load.  TGMS_PAIR_SCALED=0
-// solves the unscaled system (A/B builds).  The lane kernel (k_lane_uniform) is unscaled.
-#ifndef TGMS_PAIR_SCALED
-#define TGMS_PAIR_SCALED 1
-#endif
-#if TGMS_PAIR_SCALED
+// constants, and the given end derivatives are scaled once on load.  The unscaled system
+// was the other arm of an A/B (round 6, profiles/r06_c5_exp_hankel_ab.jsonl).  The lane
+// kernel (k_lane_uniform) is unscaled.
 constexpr double PSV = 21.0, PSA = 3.0;  // v = 21 v', a = 3 a', j = j'
 __device__ constexpr double pKSS[3][3] = {{11430720, 340200, 10080}, {340200, 10800, 360}, {10080, 360, 16}};
 __device__ constexpr double pKEE[3][3] = {{11430720, -340200, 10080}, {-340200, 10800, -360}, {10080, -360, 16}};
 __device__ constexpr double pKSE[3][3] = {{10795680, -294840, 7560}, {294840, -7560, 180}, {7560, -180, 4}};
 __device__ constexpr double pKSP[3] = {-1058400, -30240, -840};
 __device__ constexpr double pKEP[3] = {-1058400, 30240, -840};
-#else
-constexpr double PSV = 1.0, PSA = 1.0;
-__device__ constexpr double pKSS[3][3] = {{25920, 5400, 480}, {5400, 1200, 120}, {480, 120, 16}};
-__device__ constexpr double pKEE[3][3] = {{25920, -5400, 480}, {-5400, 1200, -120}, {480, -120, 16}};
-__device__ constexpr double pKSE[3][3] = {{24480, -4680, 360}, {4680, -840, 60}, {360, -60, 4}};
-__device__ constexpr double pKSP[3] = {-50400, -10080, -840};
-__device__ constexpr double pKEP[3] = {-50400, 10080, -840};
-#endif
 constexpr double PSI[3] = {1.0 / PSV, 1.0 / PSA, 1.0};  // x' = x * PSI (end derivatives on load)
 
 struct Sym3 {  // symmetric 3x3 block (upper triangle)
@@ -509,7 +454,6 @@ __device__ __forceinline__ Sym3 knot_diag_p(const double (&pp)[8], const double 
 }
 
 __device__ __forceinline__ void coupling_p(const double (&p)[8], double (&B)[3][3]) {
-#if TGMS_PAIR_SCALED
     const double q0 = 10795680.0 * p[5], q1 = 294840.0 * p[4], q2 = 7560.0 * p[3], q3 = 180.0 * p[2];
     const double q4 = 4.0 * p[1];
     B[0][0] = q0;
@@ -521,9 +465,6 @@ __device__ __forceinline__ void coupling_p(const double (&p)[8], double (&B)[3][
     B[2][0] = q2;
     B[2][1] = -q3;
     B[2][2] = q4;
-#else
-    coupling(p, B);
-#endif
 }
 
 // ---------------------------------------------------------------------------
@@ -627,26 +568,8 @@ __device__ __forceinline__ void ax_factor(AxFactors<M>& Fa, const LaneView& L, b
     Fa.spd = Fa.spd && ok1 && ok2;
 }
 
-// Right-hand side of virtual knot k for axis a (see knot_rhs).
-template <bool HAS_ED>
-__device__ __forceinline__ void knot_rhs_axis(const LaneView& L, int k, int a, const double (&pp)[8],
-                                              const double (&pn)[8], const double (&u0)[3], double (&y)[3]) {
-    const double fp[3] = {-pKEP[0] * pp[6], -pKEP[1] * pp[5], -pKEP[2] * pp[4]};
-    const double fn[3] = {-pKSP[0] * pn[6], -pKSP[1] * pn[5], -pKSP[2] * pn[4]};
-    const double wk = L.w(k, a);
-    const double dp = wk - L.w(k - 1, a);
-    const double dn = L.w(k + 1, a) - wk;
-#pragma unroll
-    for (int d = 0; d < 3; ++d) y[d] = fp[d] * dp + fn[d] * dn;
-    if (HAS_ED && k == 1) {
-#pragma unroll
-        for (int d = 0; d < 3; ++d)
-#pragma unroll
-            for (int e = 0; e < 3; ++e) y[d] -= (pKSE[e][d] * pp[5 - d - e]) * u0[e];
-    }
-}
-
-// knot_rhs_axis from waypoint values already in registers (wm, wk, wn: knots k-1, k, k+1).
+// Right-hand side of virtual knot k for one axis (see knot_rhs), from waypoint values already
+// in registers (wm, wk, wn: knots k-1, k, k+1).
 template <bool HAS_ED>
 __device__ __forceinline__ void knot_rhs_vals(int k, double wm, double wk, double wn, const double (&pp)[8],
                                               const double (&pn)[8], const double (&u0)[3], double (&y)[3]) {
@@ -697,34 +620,16 @@ template <class O>
 struct is_cost_out<CostOutT<O>> : std::true_type {};
 
 
-// The same J and dJ/dT from the segment's scaled monomial data P4..P7 (c_k = r^(k-3) P_k)
-// instead of the Hermite data: with s = t / T the snap is r q(s),
-// q = 24 P4 + 120 P5 s + 360 P6 s^2 + 840 P7 s^3, so J = r Q with Q = P^T H P,
-// H_kl = a_k a_l / (k + l + 1) for k, l = 0..3 (a = 24, 120, 360, 840; H_33 = 100800, KH's position
-// entry).  P is linear in u = (D, V0, A0, J0, V1, A1, J1) whose entries carry r^3, r^2,
-// r, 1, r^2, r, 1, so dQ/dr = (2/r) P^T H P' with P' the same map applied to
-// (3D, 2V0, A0, 0, 2V1, A1, 0); dJ/dT = -r^2 dJ/dr = r^2 Qd with Qd = -(Q + 2 P'^T H P).
-// 47 FP64 operations per axis and segment instead of ~100 for the quadratic form in u
-// with KH (round 2; the P4..P7 are computed for the coefficients anyway).  The two agree
-// up to rounding (tests/test_refine_oracle.py pins the gradient on the CPU side).
-__device__ __forceinline__ void seg_cost_p(double D, double V0, double A0, double V1, double A1, double P4,
-                                           double P5, double P6, double P7, double& Q, double& Qd) {
-    const double Q4 = 105.0 * D - 40.0 * V0 - 5.0 * A0 - 30.0 * V1 + 2.5 * A1;
-    const double Q5 = -252.0 * D + 90.0 * V0 + 10.0 * A0 + 78.0 * V1 - 7.0 * A1;
-    const double Q6 = 210.0 * D - 72.0 * V0 - 7.5 * A0 - 68.0 * V1 + 6.5 * A1;
-    const double Q7 = -60.0 * D + 20.0 * V0 + 2.0 * A0 + 20.0 * V1 - 2.0 * A1;
-    const double H4 = 576.0 * P4 + 1440.0 * P5 + 2880.0 * P6 + 5040.0 * P7;
-    const double H5 = 1440.0 * P4 + 4800.0 * P5 + 10800.0 * P6 + 20160.0 * P7;
-    const double H6 = 2880.0 * P4 + 10800.0 * P5 + 25920.0 * P6 + 50400.0 * P7;
-    const double H7 = 5040.0 * P4 + 20160.0 * P5 + 50400.0 * P6 + 100800.0 * P7;
-    Q = P4 * H4 + P5 * H5 + P6 * H6 + P7 * H7;
-    const double G = Q4 * H4 + Q5 * H5 + Q6 * H6 + Q7 * H7;
-    Qd = -(Q + 2.0 * G);
-}
-// Round 6: the same Q and Qd in the Legendre basis of the snap, from the scaled end data
-// directly (no P4..P7; used by the gradient passes, which need no coefficients).  The Gram
-// matrix above factors as H = L L^T with L^T E = diag(1, sqrt3, sqrt5, sqrt7) x an integer
-// map, so with
+// The same J and dJ/dT through the segment's scaled monomial data P4..P7 (c_k = r^(k-3) P_k):
+// with s = t / T the snap is r q(s), q = 24 P4 + 120 P5 s + 360 P6 s^2 + 840 P7 s^3, so
+// J = r Q with Q = P^T H P, H_kl = a_k a_l / (k + l + 1) for k, l = 0..3 (a = 24, 120, 360,
+// 840; H_33 = 100800, KH's position entry).  P is linear in u = (D, V0, A0, J0, V1, A1, J1)
+// whose entries carry r^3, r^2, r, 1, r^2, r, 1, so dQ/dr = (2/r) P^T H P' with P' the same
+// map applied to (3D, 2V0, A0, 0, 2V1, A1, 0); dJ/dT = -r^2 dJ/dr = r^2 Qd with
+// Qd = -(Q + 2 P'^T H P).  (tests/test_refine_oracle.py pins the gradient on the CPU side.)
+// seg_grad_u evaluates Q and Qd in the Legendre basis of the snap, from the scaled end data
+// directly (no P4..P7: the gradient passes need no coefficients).  H factors as
+// H = L L^T with L^T E = diag(1, sqrt3, sqrt5, sqrt7) x an integer map, so with
 //   g0 = j1 - j0,  g1 = 2 (A0 - A1) + (j0 + j1),  g2 = 12 (V1 - V0) - 6 (A0 + A1) + (j1 - j0),
 //   g3 = -120 D + 60 (V0 + V1) + 12 (A0 - A1) + (j0 + j1)
 // (the orthonormal shifted-Legendre coefficients of the snap, up to those square roots):
@@ -732,8 +637,9 @@ __device__ __forceinline__ void seg_cost_p(double D, double V0, double A0, doubl
 //   G = Qv^T H P = 3 g1 d1 + 5 g2 d2 + 7 g3 d3 with d the same map of (3D, 2V0, A0, 0, 2V1, A1, 0),
 //   Qd = -(Q + 2 G)
 // -- exact integer identities (checked symbolically), ~33 FP64 operations
-// per axis and segment instead of ~74 for P4..P7 + seg_cost_p.  V and A arrive in the pair
-// kernels' scaled unknowns (V = PSV V', A = PSA A'); the factors fold into the constants.
+// per axis and segment.  Round 5 formed P4..P7 and the products with H explicitly (~74
+// operations); it measured slower (profiles/r06_c5_legendre_ab.jsonl).  V and A arrive in the
+// pair kernels' scaled unknowns (V = PSV V', A = PSA A'); the factors fold into the constants.
 __device__ __forceinline__ void seg_grad_u(double D, double V0, double A0, double j0, double V1, double A1,
                                            double j1, double& Q, double& Qd) {
     const double sA = A0 - A1, pA = A0 + A1, sJ = j0 + j1, dJ = j1 - j0, sV = V0 + V1, dV = V1 - V0;
@@ -749,7 +655,8 @@ __device__ __forceinline__ void seg_grad_u(double D, double V0, double A0, doubl
     Qd = fma(-2.0, G, -Q);
 }
 
-// Q alone (the cost at the final times needs no derivative): 20 FP64 operations.
+// Q = P^T H P from P4..P7 (the cost at the final times: its pass computes the coefficients
+// anyway and needs no derivative): 20 FP64 operations.
 __device__ __forceinline__ double seg_cost_q(double P4, double P5, double P6, double P7) {
     const double H4 = 576.0 * P4 + 1440.0 * P5 + 2880.0 * P6 + 5040.0 * P7;
     const double H5 = 1440.0 * P4 + 4800.0 * P5 + 10800.0 * P6 + 20160.0 * P7;
@@ -772,7 +679,6 @@ template <int M, class Out>
 __device__ __forceinline__ void emit_axis_v(const Out& o, double ws, double we, double r, bool right, int e, int a,
                                             const double (&xs)[3], const double (&xe)[3], bool has_r,
                                             bool zero = false) {
-#if TGMS_GRAD_LEGENDRE
     if constexpr (is_grad<Out>::value) {
         // The snap cost of a segment and its T-derivative do not change under time reversal
         // (the odd lane's virtual segment is the physical one run backwards, with
@@ -791,7 +697,6 @@ __device__ __forceinline__ void emit_axis_v(const Out& o, double ws, double we, 
         asm volatile("" : "+v"(o.J), "+v"(o.dJ[e]));
         return;
     }
-#endif
     const double w0 = right ? we : ws, w1 = right ? ws : we;
     // the odd lane runs the segment backwards: physical start = virtual knot e+1, with P
     const double v0 = right ? -xe[0] : xs[0], a0 = right ? xe[1] : xs[1], j0 = right ? -xe[2] : xs[2];
@@ -810,20 +715,6 @@ __device__ __forceinline__ void emit_axis_v(const Out& o, double ws, double we, 
                       (6.5 * PSA) * A1 - 0.5 * j1;
     const double P7 = -20.0 * D + (10.0 * PSV) * V0 + (2.0 * PSA) * A0 + (1.0 / 6.0) * j0 + (10.0 * PSV) * V1 -
                       (2.0 * PSA) * A1 + (1.0 / 6.0) * j1;
-#if !TGMS_GRAD_LEGENDRE
-    if constexpr (is_grad<Out>::value) {  // round 5's form (A/B builds)
-        double Q, Qd;
-        seg_cost_p(D, PSV * V0, PSA * A0, PSV * V1, PSA * A1, P4, P5, P6, P7, Q, Qd);
-        const bool mine = has_r || !right;  // the odd lane's last step may duplicate the even lane's
-        o.J += mine ? r * Q : 0.0;
-        o.dJ[e] += mine ? r2 * Qd : 0.0;
-        // anchored here: nothing stores these sums until the step's update, so without
-        // the anchor the compiler sinks every segment's cost arithmetic (and keeps all
-        // knot data live for it) to the end of the solve
-        asm volatile("" : "+v"(o.J), "+v"(o.dJ[e]));
-        return;
-    }
-#endif
     if constexpr (!is_grad<Out>::value) {
         double c[8] = {w0, PSV * v0, (0.5 * PSA) * a0, j0 * (1.0 / 6.0), P4 * r, P5 * r2, P6 * r3, P7 * r4};
 #pragma unroll
@@ -886,16 +777,14 @@ __device__ __forceinline__ int32_t pair_solve_ax(const LaneView& L, bool right, 
         {
             double pp[8];
             rpowers(L.r(0), pp);
-#if TGMS_PAIR_PREFETCH  // the next step's LDS values are read one step ahead
+            // the next step's LDS values are read one step ahead
             double rk = L.r(1), wm = L.w(0, a), wk = L.w(1, a), wn = L.w(2, a);
-#endif
 #pragma unroll
             for (int s = 0; s < NS; ++s) {
                 SCHED_FENCE();
                 const int k = s + 1;
                 double pn[8];
                 double y[3];
-#if TGMS_PAIR_PREFETCH
                 const double rk1 = (s + 1 < NS) ? L.r(k + 1) : 0.0;
                 const double wn1 = (s + 1 < NS) ? L.w(k + 2, a) : 0.0;
                 rpowers(rk, pn);
@@ -904,10 +793,6 @@ __device__ __forceinline__ int32_t pair_solve_ax(const LaneView& L, bool right, 
                 wm = wk;
                 wk = wn;
                 wn = wn1;
-#else
-                rpowers(L.r(k), pn);
-                knot_rhs_axis<HAS_ED>(L, k, a, pp, pn, u0, y);
-#endif
                 if (s >= 1) {
                     double B[3][3], v0, v1, v2;
                     coupling_p(pp, B);
@@ -972,26 +857,19 @@ __device__ __forceinline__ int32_t pair_solve_ax(const LaneView& L, bool right, 
         // final (segment s+1 right after knot s): the two are independent, which
         // gives the scheduler a second dependency chain to interleave ----
         MARK(ax_back);
-#if TGMS_PAIR_PREFETCH  // segment s+1's waypoints and 1/T, read one step ahead
+        // segment s+1's waypoints and 1/T, read one step ahead
         double w_lo = L.w(NS, a), w_hi = L.w(NS + 1, a), r_n = L.r(NS);
-#endif
 #pragma unroll
         for (int s = NS - 1; s >= 0; --s) {
             SCHED_FENCE();
             const bool at_end = (s == nl - 1);
             const bool inside = (s < nl - 1);
-#if TGMS_PAIR_PREFETCH
             const double w_next = L.w(s, a), r_next = L.r(s);
-#endif
             if (s + 1 < NS) {
                 double B[3][3];
                 {
                     double pb[8];
-#if TGMS_PAIR_PREFETCH
                     rpowers(r_n, pb);
-#else
-                    rpowers(L.r(s + 1), pb);
-#endif
                     coupling_p(pb, B);
                 }
                 double b[3], x0, x1, x2;
@@ -1006,23 +884,15 @@ __device__ __forceinline__ int32_t pair_solve_ax(const LaneView& L, bool right, 
 #pragma unroll
                 for (int d = 0; d < 3; ++d) Y[s][d] = at_end ? xm[d] : Y[s][d];
             }
-#if TGMS_PAIR_PREFETCH
             if (s + 1 < NE)
                 emit_axis_v<M, Out>(O, w_lo, w_hi, r_n, right, s + 1, a, Y[s], Y[s + 1], s + 1 < nR, !spd_pair);
             w_hi = w_lo;
             w_lo = w_next;
             r_n = r_next;
-#else
-            if (s + 1 < NE) emit_axis<M, Out>(O, L, right, s + 1, a, Y[s], Y[s + 1], s + 1 < nR, !spd_pair);
-#endif
         }
         MARK(ax_emit);
         SCHED_FENCE();
-#if TGMS_PAIR_PREFETCH
         emit_axis_v<M, Out>(O, w_lo, w_hi, r_n, right, 0, a, u0, Y[0], 0 < nR, !spd_pair);
-#else
-        emit_axis<M, Out>(O, L, right, 0, a, u0, Y[0], 0 < nR, !spd_pair);
-#endif
     }
     MARK(ax_end);
     const double fin_pair = fin + pair_swap(fin);
@@ -1138,7 +1008,6 @@ __device__ __forceinline__ int32_t pair_solve_joint(const LaneView& L, bool righ
     {
         double pp[8];
         rpowers(L.r(0), pp);
-#if TGMS_JOINT_PREFETCH
         double rk = L.r(1), wm[3], wk[3], wn[3];
 #pragma unroll
         for (int a = 0; a < 3; ++a) {
@@ -1146,31 +1015,22 @@ __device__ __forceinline__ int32_t pair_solve_joint(const LaneView& L, bool righ
             wk[a] = L.w(1, a);
             wn[a] = L.w(2, a);
         }
-#endif
 #pragma unroll
         for (int s = 0; s < NS; ++s) {
             SCHED_FENCE();
             const int k = s + 1;
             double pn[8];
-#if TGMS_JOINT_PREFETCH
             const double rk1 = (s + 1 < NS) ? L.r(k + 1) : 0.0;
             double wn1[3];
 #pragma unroll
             for (int a = 0; a < 3; ++a) wn1[a] = (s + 1 < NS) ? L.w(k + 2, a) : 0.0;
             rpowers(rk, pn);
-#else
-            rpowers(L.r(k), pn);
-#endif
             double B[3][3];
             if (s >= 1) coupling_p(pp, B);
 #pragma unroll
             for (int a = 0; a < 3; ++a) {
                 double y[3];
-#if TGMS_JOINT_PREFETCH
                 knot_rhs_vals<HAS_ED>(k, wm[a], wk[a], wn[a], pp, pn, u0[a], y);
-#else
-                knot_rhs_axis<HAS_ED>(L, k, a, pp, pn, u0[a], y);
-#endif
                 if (s >= 1) {
                     double v0, v1, v2;
                     ldl3_solve(Fa.F[s - 1], Y[s - 1][a][0], Y[s - 1][a][1], Y[s - 1][a][2], v0, v1, v2);
@@ -1183,7 +1043,6 @@ __device__ __forceinline__ int32_t pair_solve_joint(const LaneView& L, bool righ
             pin33(Y[s]);
 #pragma unroll
             for (int q = 0; q < 8; ++q) pp[q] = pn[q];
-#if TGMS_JOINT_PREFETCH
             rk = rk1;
 #pragma unroll
             for (int a = 0; a < 3; ++a) {
@@ -1191,7 +1050,6 @@ __device__ __forceinline__ int32_t pair_solve_joint(const LaneView& L, bool righ
                 wk[a] = wn[a];
                 wn[a] = wn1[a];
             }
-#endif
         }
     }
     SCHED_FENCE();
@@ -1244,34 +1102,26 @@ __device__ __forceinline__ int32_t pair_solve_joint(const LaneView& L, bool righ
         }
     }
     // ---- back substitution, three axes per knot; segment s+1 emitted right after ----
-#if TGMS_JOINT_PREFETCH
     double w_lo[3], w_hi[3], r_n = L.r(NS);
 #pragma unroll
     for (int a = 0; a < 3; ++a) {
         w_lo[a] = L.w(NS, a);
         w_hi[a] = L.w(NS + 1, a);
     }
-#endif
 #pragma unroll
     for (int s = NS - 1; s >= 0; --s) {
         SCHED_FENCE();
         const bool at_end = (s == nl - 1);
         const bool inside = (s < nl - 1);
-#if TGMS_JOINT_PREFETCH
         double w_next[3];
 #pragma unroll
         for (int a = 0; a < 3; ++a) w_next[a] = L.w(s, a);
         const double r_next = L.r(s);
-#endif
         if (s + 1 < NS) {
             double B[3][3];
             {
                 double pb[8];
-#if TGMS_JOINT_PREFETCH
                 rpowers(r_n, pb);
-#else
-                rpowers(L.r(s + 1), pb);
-#endif
                 coupling_p(pb, B);
             }
 #pragma unroll
@@ -1305,21 +1155,15 @@ __device__ __forceinline__ int32_t pair_solve_joint(const LaneView& L, bool righ
         } else if (s + 1 < NE) {
 #pragma unroll
             for (int a = 0; a < 3; ++a)
-#if TGMS_JOINT_PREFETCH
                 emit_axis_v<M, Out>(O, w_lo[a], w_hi[a], r_n, right, s + 1, a, Y[s][a], Y[s + 1][a], s + 1 < nR,
                                     !spd_pair);
-#else
-                emit_axis<M, Out>(O, L, right, s + 1, a, Y[s][a], Y[s + 1][a], s + 1 < nR, !spd_pair);
-#endif
         }
-#if TGMS_JOINT_PREFETCH
 #pragma unroll
         for (int a = 0; a < 3; ++a) {
             w_hi[a] = w_lo[a];
             w_lo[a] = w_next[a];
         }
         r_n = r_next;
-#endif
     }
     SCHED_FENCE();
     if constexpr (is_pair_lines<Out>::value) {
@@ -1331,11 +1175,7 @@ __device__ __forceinline__ int32_t pair_solve_joint(const LaneView& L, bool righ
     } else {
 #pragma unroll
         for (int a = 0; a < 3; ++a)
-#if TGMS_JOINT_PREFETCH
             emit_axis_v<M, Out>(O, w_lo[a], w_hi[a], r_n, right, 0, a, u0[a], Y[0][a], 0 < nR, !spd_pair);
-#else
-            emit_axis<M, Out>(O, L, right, 0, a, u0[a], Y[0][a], 0 < nR, !spd_pair);
-#endif
     }
     const double fin_pair = fin + pair_swap(fin);
     if (!valid) return TGMS_ERR_INVALID_ARG;
@@ -1411,7 +1251,7 @@ __device__ __forceinline__ int32_t pair_solve(const LaneView& L, bool right, V&&
         if (!finite(fin_pair)) return TGMS_ERR_NONFINITE;
         return TGMS_OK;
     } else {
-        if constexpr (M > TGMS_TWO_WAVE_MAX_M && TGMS_JOINT_AXES)
+        if constexpr (M > TGMS_TWO_WAVE_MAX_M)
             return pair_solve_joint<M, HAS_ED, Out>(L, right, valid_src, ed, O);
         else
             return pair_solve_ax<M, HAS_ED, Out>(L, right, valid_src, ed, O);
@@ -1423,12 +1263,12 @@ __device__ __forceinline__ int32_t pair_solve(const LaneView& L, bool right, V&&
 
 template <int M>
 __device__ __forceinline__ void stage_row_w(In<M>& sm, int t, int q, double v) {
-    sm.W[w_at<M>(q, t)] = v;
+    sm.W[q * PSTRIDE + t] = v;
     if (!finite(v)) atomicOr(&sm.bad[t], 1);
 }
 template <int M>
 __device__ __forceinline__ void stage_row_t(In<M>& sm, int t, int q, double v) {
-    sm.R[r_at<M>(q, t)] = fast_rcp(v);
+    sm.R[q * PSTRIDE + t] = fast_rcp(v);
     if (!finite_pos(v)) atomicOr(&sm.bad[t], 1);
 }
 
@@ -1448,8 +1288,8 @@ __device__ __forceinline__ void stage_check_ed(In<M>& sm, int t, bool right, con
 template <int M>
 __device__ __forceinline__ void sanitize(In<M>& sm, int lane) {
     if (lane < TPW && sm.bad[lane]) {
-        for (int q = 0; q < (M + 1) * 3; ++q) sm.W[w_at<M>(q, lane)] = 0.0;
-        for (int q = 0; q < M; ++q) sm.R[r_at<M>(q, lane)] = 1.0;
+        for (int q = 0; q < (M + 1) * 3; ++q) sm.W[q * PSTRIDE + lane] = 0.0;
+        for (int q = 0; q < M; ++q) sm.R[q * PSTRIDE + lane] = 1.0;
     }
 }
 
@@ -1627,14 +1467,8 @@ __global__ __launch_bounds__(64, TGMS_WAVES(M)) void k_reduced_uniform(int32_t B
 // library exp's range reduction, ldexp and overflow selects (~28 VALU per segment) are dead
 // weight on this range.  Coefficients: Chebyshev interpolation at 60 digits
 // (scripts/exp_poly.py), worst error 0.83 ulp over [-1/2, 1/2] with every FMA rounded.
-// TGMS_EXP_LIBM=1 keeps the library exp (A/B builds).
-#ifndef TGMS_EXP_LIBM
-#define TGMS_EXP_LIBM 0
-#endif
+// The library exp was the other arm of an A/B (round 6, profiles/r06_c5_exp_hankel_ab.jsonl).
 __device__ __forceinline__ double exp_step(double x) {
-#if TGMS_EXP_LIBM
-    return exp(x);
-#else
     double p = 2.0970151215169475e-09;
     p = fma(p, x, 2.5182899238184787e-08);
     p = fma(p, x, 2.7557027169443954e-07);
@@ -1648,7 +1482,6 @@ __device__ __forceinline__ double exp_step(double x) {
     p = fma(p, x, 0.5);
     p = fma(p, x, 0.9999999999999999);
     return fma(p, x, 1.0);
-#endif
 }
 template <int M>
 __device__ __forceinline__ void refine_update(const GradAcc<Chain<M>::NE>& G, bool right, int32_t st, bool live,
@@ -1895,7 +1728,7 @@ __device__ __forceinline__ void refine_loop_block(Stage<M>& sm, int64_t blk, int
                 dtau = fmin(fmax(dtau, -0.5), 0.5);
                 const double tn = ok ? tl * exp_step(dtau) : tl;
                 Tl[e] = tn;
-                sm.in.R[r_at<M>(phys, slot)] = fast_rcp(tn);
+                sm.in.R[phys * PSTRIDE + slot] = fast_rcp(tn);
             }
         }
         __syncthreads();
@@ -1952,12 +1785,10 @@ static_assert(TPW == RAGGED_TPW, "host group tables assume TPW trajectories per 
 template <int MLO, int MHI>
 constexpr size_t max_stage_bytes() {
     size_t b = 0;
-#define TGMS_STAGE_MAX(m) \
+#define X(m) \
     if constexpr (m >= MLO && m <= MHI) b = b > sizeof(Stage<m>) ? b : sizeof(Stage<m>);
-    TGMS_STAGE_MAX(1) TGMS_STAGE_MAX(2) TGMS_STAGE_MAX(3) TGMS_STAGE_MAX(4) TGMS_STAGE_MAX(5) TGMS_STAGE_MAX(6)
-    TGMS_STAGE_MAX(7) TGMS_STAGE_MAX(8) TGMS_STAGE_MAX(9) TGMS_STAGE_MAX(10) TGMS_STAGE_MAX(11)
-    TGMS_STAGE_MAX(12) TGMS_STAGE_MAX(13) TGMS_STAGE_MAX(14) TGMS_STAGE_MAX(15) TGMS_STAGE_MAX(16)
-#undef TGMS_STAGE_MAX
+    TGMS_CASES(X)
+#undef X
     return b;
 }
 
@@ -1980,17 +1811,14 @@ __global__ __launch_bounds__(64, TGMS_WAVES(MHI)) void k_reduced_multi(GroupTabl
     int64_t blk;
     const int g = group_of(tab, blockIdx.x, blk);
     switch (tab.m[g]) {
-#define TGMS_MULTI_CASE(mm)                                                                                \
+#define X(mm)                                                                                \
     case mm:                                                                                              \
         if constexpr (mm >= MLO && mm <= MHI)                                                             \
             reduced_ragged_block<mm, HAS_ED>(*reinterpret_cast<Stage<mm>*>(raw), blk, tab.n[g], tab.perm[g], \
                                              seg_offsets, W, T, ED, C, status);                           \
         break;
-        TGMS_MULTI_CASE(1) TGMS_MULTI_CASE(2) TGMS_MULTI_CASE(3) TGMS_MULTI_CASE(4) TGMS_MULTI_CASE(5)
-        TGMS_MULTI_CASE(6) TGMS_MULTI_CASE(7) TGMS_MULTI_CASE(8) TGMS_MULTI_CASE(9) TGMS_MULTI_CASE(10)
-        TGMS_MULTI_CASE(11) TGMS_MULTI_CASE(12) TGMS_MULTI_CASE(13) TGMS_MULTI_CASE(14) TGMS_MULTI_CASE(15)
-        TGMS_MULTI_CASE(16)
-#undef TGMS_MULTI_CASE
+        TGMS_CASES(X)
+#undef X
         default: break;
     }
 }
@@ -2008,17 +1836,14 @@ __global__ __launch_bounds__(64, TGMS_WAVES(MHI)) void k_refine_multi(GroupTable
     int64_t blk;
     const int g = group_of(tab, blockIdx.x, blk);
     switch (tab.m[g]) {
-#define TGMS_MULTI_CASE(mm)                                                                                 \
+#define X(mm)                                                                                 \
     case mm:                                                                                               \
         if constexpr (mm >= MLO && mm <= MHI)                                                              \
             refine_ragged_block<mm, HAS_ED>(*reinterpret_cast<Stage<mm>*>(raw), blk, tab.n[g], tab.perm[g], \
                                             seg_offsets, W, T, ED, kT, eta, Tout, cost, status);           \
         break;
-        TGMS_MULTI_CASE(1) TGMS_MULTI_CASE(2) TGMS_MULTI_CASE(3) TGMS_MULTI_CASE(4) TGMS_MULTI_CASE(5)
-        TGMS_MULTI_CASE(6) TGMS_MULTI_CASE(7) TGMS_MULTI_CASE(8) TGMS_MULTI_CASE(9) TGMS_MULTI_CASE(10)
-        TGMS_MULTI_CASE(11) TGMS_MULTI_CASE(12) TGMS_MULTI_CASE(13) TGMS_MULTI_CASE(14) TGMS_MULTI_CASE(15)
-        TGMS_MULTI_CASE(16)
-#undef TGMS_MULTI_CASE
+        TGMS_CASES(X)
+#undef X
         default: break;
     }
 }
@@ -2035,18 +1860,15 @@ __device__ __forceinline__ void refine_loop_tile(unsigned char* raw, const Group
     int64_t blk;
     const int g = group_of(tab, tile, blk);
     switch (tab.m[g]) {
-#define TGMS_MULTI_CASE(mm)                                                                                    \
+#define X(mm)                                                                                    \
     case mm:                                                                                                  \
         if constexpr (mm >= MLO && mm <= MHI)                                                                 \
             refine_loop_block<mm, HAS_ED, TGMS_WAVES(MHI) == 1>(*reinterpret_cast<Stage<mm>*>(raw), blk,       \
                                                                  tab.n[g], tab.perm[g], seg_offsets, W, T, ED, kT, \
                                                                  eta, iters, cost, C, status, so_base);            \
         break;
-        TGMS_MULTI_CASE(1) TGMS_MULTI_CASE(2) TGMS_MULTI_CASE(3) TGMS_MULTI_CASE(4) TGMS_MULTI_CASE(5)
-        TGMS_MULTI_CASE(6) TGMS_MULTI_CASE(7) TGMS_MULTI_CASE(8) TGMS_MULTI_CASE(9) TGMS_MULTI_CASE(10)
-        TGMS_MULTI_CASE(11) TGMS_MULTI_CASE(12) TGMS_MULTI_CASE(13) TGMS_MULTI_CASE(14) TGMS_MULTI_CASE(15)
-        TGMS_MULTI_CASE(16)
-#undef TGMS_MULTI_CASE
+        TGMS_CASES(X)
+#undef X
         default: break;
     }
 }
@@ -2056,7 +1878,7 @@ __device__ __forceinline__ void refine_loop_tile(unsigned char* raw, const Group
 //   * plan->waves[cls] == 0: one block per wavefront tile (longest groups first), blocks
 //     past the class's last tile return; the hardware dispatches tiles into free slots;
 //   * plan->waves[cls] > 0 (the one-wave class when it has more tiles than the GPU has
-//     SIMDs, TGMS_C5_PERSIST): that many PERSISTENT wavefronts, each holding its SIMD and
+//     SIMDs): that many PERSISTENT wavefronts, each holding its SIMD and
 //     taking tiles from plan->next[cls] (zeroed by the planner) until none is left.  A
 //     one-wave tile needs a whole SIMD, which a SIMD shared with the two-wave class never
 //     frees while two-wave tiles are pending: at full config-5 size (6,563 one-wave tiles)
@@ -2124,17 +1946,14 @@ __global__ __launch_bounds__(64, TGMS_WAVES(MHI)) void k_reduced_multi_dev(const
     const int g = group_of(tab, blockIdx.x, blk);
     const int32_t so_base = plan->so_base;
     switch (tab.m[g]) {
-#define TGMS_MULTI_CASE(mm)                                                                                 \
+#define X(mm)                                                                                 \
     case mm:                                                                                               \
         if constexpr (mm >= MLO && mm <= MHI)                                                              \
             reduced_ragged_block<mm, HAS_ED>(*reinterpret_cast<Stage<mm>*>(raw), blk, tab.n[g], tab.perm[g], \
                                              seg_offsets, W, T, ED, C, status, so_base);                  \
         break;
-        TGMS_MULTI_CASE(1) TGMS_MULTI_CASE(2) TGMS_MULTI_CASE(3) TGMS_MULTI_CASE(4) TGMS_MULTI_CASE(5)
-        TGMS_MULTI_CASE(6) TGMS_MULTI_CASE(7) TGMS_MULTI_CASE(8) TGMS_MULTI_CASE(9) TGMS_MULTI_CASE(10)
-        TGMS_MULTI_CASE(11) TGMS_MULTI_CASE(12) TGMS_MULTI_CASE(13) TGMS_MULTI_CASE(14) TGMS_MULTI_CASE(15)
-        TGMS_MULTI_CASE(16)
-#undef TGMS_MULTI_CASE
+        TGMS_CASES(X)
+#undef X
         default: break;
     }
 }
@@ -2307,7 +2126,7 @@ __global__ __launch_bounds__(PERM_BLOCK) void k_plan_scatter(int32_t n, int64_t 
             plan->next[1] = 0;
             plan->waves[0] = 0;
             plan->waves[1] = 0;
-            if (TGMS_C5_PERSIST && !bad) {
+            if (!bad) {
                 int64_t w1 = 0, w2 = 0, t1 = 0;
                 for (int k = 1; k < PERM_BINS; ++k) {
                     const int64_t tiles = (cnt[k] + RAGGED_TPW - 1) / RAGGED_TPW;
@@ -3058,9 +2877,6 @@ __global__ __launch_bounds__(64, 1) void k_lane_uniform(int32_t B, const double*
 }
 
 // Uniform batches with an even number of segments take the lane-per-trajectory kernel.
-#ifndef TGMS_LANE_UNIFORM
-#define TGMS_LANE_UNIFORM 1
-#endif
 // Largest M on the lane kernel: its whole elimination state lives in registers, which
 // at M >= 12 spill to scratch (92-980 B per lane).  At M = 12 it still matches the
 // lane-pair kernel (51.6 vs 52.4 us per 65,536, fresh batches); at 14 and 16 the pair is
@@ -3071,7 +2887,7 @@ __global__ __launch_bounds__(64, 1) void k_lane_uniform(int32_t B, const double*
 #endif
 template <int M>
 constexpr bool use_lane_kernel() {
-    return TGMS_LANE_UNIFORM && M >= 2 && M % 2 == 0 && M <= TGMS_LANE_MAX_M;
+    return M >= 2 && M % 2 == 0 && M <= TGMS_LANE_MAX_M;
 }
 // Even M from here up (and above the lane kernel's range) take the joint lane-pair solve
 // with whole-line output (k_reduced_uniform_lines).
@@ -3235,7 +3051,7 @@ hipError_t loop_dev_launch(int cls, int32_t n, DevPlan* plan, const int32_t* so,
     // the one-wave class: as many blocks as SIMDs at most (persistent when it has more tiles
     // than that, k_plan_scatter); the two-wave class one block per tile
     unsigned grid = dev_loop_grid(n);
-    if (TGMS_C5_PERSIST && cls == 1) grid = std::min<unsigned>(grid, (unsigned)device_simds());
+    if (cls == 1) grid = std::min<unsigned>(grid, (unsigned)device_simds());
     if constexpr (MLO <= MHI)  // (MLO > MHI: an empty class, every M at two waves)
         TGMS_LAUNCH((k_refine_loop_dev<MLO, MHI, HAS_ED>), dim3(grid), dim3(W64), 0, stream, plan, cls, so, W, T, ED,
                     kT, eta, iters, cost, C, status);
@@ -3287,8 +3103,6 @@ hipError_t launch_ragged_multi(int cls, const GroupTable& tab, bool refine, cons
     if (cls == 0) return multi_launch<1, A>(tab, refine, so, W, T, ED, kT, eta, Tout, cost, C, status, stream);
     return multi_launch<A + 1, 16>(tab, refine, so, W, T, ED, kT, eta, Tout, cost, C, status, stream);
 }
-
-#define TGMS_CASES(X) X(1) X(2) X(3) X(4) X(5) X(6) X(7) X(8) X(9) X(10) X(11) X(12) X(13) X(14) X(15) X(16)
 
 hipError_t launch_reduced_uniform(int M, int32_t B, const double* W, const double* T, const double* ED,
                                   double* C, int32_t* status, hipStream_t stream) {
