@@ -39,8 +39,9 @@
  *     replays may run beside uncaptured calls, but graphs holding band launches of one
  *     handle must be replayed in stream order with each other.  Calls that upload a
  *     host-side launch plan or grow scratch at call time (ragged batches,
- *     tgms_refine_loop_device, the multi-GPU calls, a band capture with no slab large
- *     enough) return TGMS_ERR_UNSUPPORTED while their stream is capturing.
+ *     tgms_refine_loop_device, tgms_neighbors_batch_device, the multi-GPU calls, a band
+ *     capture with no slab large enough) return TGMS_ERR_UNSUPPORTED while their stream is
+ *     capturing.
  *     tgms_extrema_batch_device and tgms_bounds_batch_device (one kernel, no plan, no
  *     scratch) may be captured for any batch, ragged included;
  *   - there is no CPU fallback: with no usable GPU, tgms_create fails with
@@ -112,8 +113,8 @@ const char* tgms_status_string(int status);
 tgms_status tgms_create(tgms_handle** out, int device);
 /* The explicit host backend (BASELINE config 1: a ROS 2 node with no GPU; the reference
  * generates on the executor thread's CPU, src/TrajectoryGenerator.cpp:54-57, :71).  A host
- * handle runs tgms_solve_batch (reduced method), tgms_sample_batch, tgms_extrema_batch and
- * tgms_bounds_batch on the calling thread with the GPU path's conventions; every other entry point returns
+ * handle runs tgms_solve_batch (reduced method), tgms_sample_batch, tgms_extrema_batch,
+ * tgms_bounds_batch, tgms_separation_batch and tgms_neighbors_batch on the calling thread with the GPU path's conventions; every other entry point returns
  * TGMS_ERR_UNSUPPORTED on it.  Chosen by the caller only: tgms_create never falls back to
  * it. */
 tgms_status tgms_create_host(tgms_handle** out);
@@ -349,6 +350,58 @@ tgms_status tgms_separation_batch(tgms_handle* h, int32_t B, const int32_t* seg_
                                   const double* seg_times, const double* coeffs, const double* start_times,
                                   int64_t P, const int32_t* pairs, const double* scale, double r_min,
                                   double* sep, int32_t* flags);
+
+/* ---- swarm neighbour search: nearest vehicle per vehicle, far pairs culled ----
+ * The question before the separation call: which pairs are worth testing.  The call takes the
+ * swarm and a search horizon r_min (finite and > 0, else TGMS_ERR_INVALID_ARG) and returns per
+ * vehicle i, over all j != i, with the value of the ordered pair (i, j) exactly as
+ * tgms_separation_batch defines it (global intervals, start times, held end points, per-axis
+ * scale, strict comparison on the stored value):
+ *     count[i]   the number of vehicles j whose closest approach to i is < r_min
+ *     near[i]    d_min t_min of the closest of them (TGMS_SEP_STRIDE doubles)
+ *     nbr[i]     its index; ties on the stored d_min go to the lowest j
+ *     tested[i]  the number of j for which the exact closest approach was computed
+ *     flags[i]   TGMS_SEP_CLOSE when count[i] > 0
+ * A vehicle that nobody approaches within r_min (B == 1 included) gets near = (+inf, 0.0), nbr
+ * = TGMS_NEAR_NONE, count = 0.  Every row is computed on its own, so near[i] and near[nbr[i]]
+ * come from the two ordered pairs and agree to the separation call's accuracy, not to the bit;
+ * no result depends on the launch shape or on the order in which pairs were processed.
+ *   Culling.  The exact computation (a degree-13 ladder per interval) runs only for pairs that
+ * a conservative bound cannot rule out: per-segment boxes from the Bernstein control values of
+ * the segment polynomials and point boxes for the held ends, widened by a margin that covers
+ * the rounding of both the conversion and the exact computation's own evaluations, compared
+ * interval by interval along the pair's merged knots.  The bound is sound: a pair whose
+ * tgms_separation_batch d_min is < r_min is never culled, so count, nbr and near are those of
+ * the all-pairs computation.  How many pairs it removes depends on the swarm (straight
+ * segments give tight boxes, turning ones loose boxes); tested makes it observable, with
+ * count[i] <= tested[i] <= B - 1.
+ *   An unusable vehicle (in the device call a segment count outside 1..TGMS_MAX_SEGMENTS, for
+ * which nothing is read; a time that is not finite and > 0; a start time or coefficient that
+ * is not finite; a non-finite result) gets TGMS_SEP_NONFINITE alone, near = NaN NaN, nbr =
+ * TGMS_NEAR_NONE, count = 0 and tested = 0, and is left out of every other vehicle's search:
+ * the other rows are those of the swarm without it.
+ *   At least one of near / nbr / count / flags must be non-NULL; a scale entry that is not
+ * finite and > 0 is TGMS_ERR_INVALID_ARG; fp64 device arrays are 16-byte aligned; B == 0 is
+ * TGMS_OK and launches nothing.  tgms_neighbors_batch_device is two kernel launches on handle
+ * scratch that grows with B at call time (1,064 B per vehicle), ordered among the handle's
+ * calls like all its scratch, so it returns TGMS_ERR_UNSUPPORTED while its stream is
+ * capturing.  On a multi handle it runs on device 0; on a host handle it returns
+ * TGMS_ERR_UNSUPPORTED.  tgms_neighbors_batch on a host handle computes on the calling thread
+ * (the same boxes, walk and exact computation; host and device agree to the separation call's
+ * accuracy, not to the bit); on a GPU handle it does one upload, the launches and one
+ * download. */
+#define TGMS_NEAR_NONE (-1)
+tgms_status tgms_neighbors_batch_device(tgms_handle* h, int32_t B, const int32_t* d_seg_offsets,
+                                        const double* d_seg_times, const double* d_coeffs,
+                                        const double* d_start_times /* [B], nullable */,
+                                        const double* scale /* host [3], nullable */, double r_min,
+                                        double* d_near /* [B][TGMS_SEP_STRIDE]: d_min t_min, nullable */,
+                                        int32_t* d_nbr /* [B], nullable */, int32_t* d_count /* [B], nullable */,
+                                        int32_t* d_tested /* [B], nullable */, int32_t* d_flags /* [B], nullable */,
+                                        void* stream);
+tgms_status tgms_neighbors_batch(tgms_handle* h, int32_t B, const int32_t* seg_offsets, const double* seg_times,
+                                 const double* coeffs, const double* start_times, const double* scale, double r_min,
+                                 double* near, int32_t* nbr, int32_t* count, int32_t* tested, int32_t* flags);
 
 /* ---- multi-GPU ----
  * One process drives devices 0 .. device_count-1 through one handle that owns one RCCL

@@ -53,7 +53,7 @@ struct tgms_handle {
     int32_t* h_perm = nullptr;  // pinned staging of the plan
     size_t h_perm_cap = 0;
     hipEvent_t perm_ev = nullptr;  // guards h_perm reuse until the upload completed
-    // Handle-owned device scratch (d_perm, d_loop_ws, d_band) is in use by the work
+    // Handle-owned device scratch (d_perm, d_loop_ws, d_band, d_nbr_ws) is in use by the work
     // enqueued up to scratch_ev.  Every asynchronous entry point that touches it makes
     // its stream wait for scratch_ev first and records it again after its own work, so
     // calls on different streams are ordered on the GPU (no host blocking).
@@ -63,6 +63,9 @@ struct tgms_handle {
     // blocking host API reuses)
     double* d_loop_ws = nullptr;
     size_t loop_ws_cap = 0;
+    // tgms_neighbors_batch_device's per-vehicle boxes and knots (grow-only, ordered by scratch_ev)
+    void* d_nbr_ws = nullptr;
+    size_t nbr_ws_cap = 0;
     // ragged plans: the per-M group launches fork onto these streams and join back, so
     // the groups (each a few hundred wavefronts) run side by side instead of in series
     hipStream_t aux[TGMS_AUX_STREAMS] = {};
@@ -320,6 +323,19 @@ tgms_status ensure_loop_ws(tgms_handle* h, size_t bytes) {
     }
     TGMS_HIP(h, hipMalloc(reinterpret_cast<void**>(&h->d_loop_ws), bytes));
     h->loop_ws_cap = bytes;
+    return TGMS_OK;
+}
+
+tgms_status ensure_nbr_ws(tgms_handle* h, size_t bytes) {
+    if (bytes <= h->nbr_ws_cap) return TGMS_OK;
+    if (h->d_nbr_ws) {
+        TGMS_HIP(h, hipDeviceSynchronize());
+        TGMS_HIP(h, hipFree(h->d_nbr_ws));
+        h->d_nbr_ws = nullptr;
+        h->nbr_ws_cap = 0;
+    }
+    TGMS_HIP(h, hipMalloc(&h->d_nbr_ws, bytes));
+    h->nbr_ws_cap = bytes;
     return TGMS_OK;
 }
 
@@ -1513,6 +1529,7 @@ void tgms_destroy(tgms_handle* h) {
     if (h->scratch_ev) (void)hipEventDestroy(h->scratch_ev);
     if (h->band_done) (void)hipHostFree(h->band_done);
     if (h->d_loop_ws) (void)hipFree(h->d_loop_ws);
+    if (h->d_nbr_ws) (void)hipFree(h->d_nbr_ws);
     for (int j = 0; j < TGMS_AUX_STREAMS; ++j) {
         if (h->aux[j]) (void)hipStreamDestroy(h->aux[j]);
         if (h->join_ev[j]) (void)hipEventDestroy(h->join_ev[j]);
@@ -2016,6 +2033,87 @@ tgms_status tgms_separation_batch(tgms_handle* h, int32_t B, const int32_t* so, 
     if (s != TGMS_OK) return s;
     TGMS_HIP(h, tgms::launch_separation(B, dSo, dT, dC, dT0, P, dP, sc, r_min, res.d_rec(), res.d_flags(), h->stream));
     return download(h, res);
+}
+
+// ---- swarm neighbour search: nearest vehicle per vehicle, far pairs culled ----
+
+// What both calls check before they look at a pointer.
+static tgms_status check_neighbors(tgms_handle* h, int32_t B, const double* scale, double r_min, const void* near,
+                                   const void* nbr, const void* count, const void* flags, double (&sc)[3]) {
+    if (B < 0) return set_err(h, TGMS_ERR_INVALID_ARG, "bad B");
+    if (!resolve_scale(scale, sc)) return set_err(h, TGMS_ERR_INVALID_ARG, "scale entries must be finite and > 0");
+    if (!(r_min > 0.0) || !std::isfinite(r_min)) return set_err(h, TGMS_ERR_INVALID_ARG, "r_min must be finite and > 0");
+    if (!near && !nbr && !count && !flags)
+        return set_err(h, TGMS_ERR_INVALID_ARG, "near, nbr, count and flags all NULL");
+    return TGMS_OK;
+}
+
+// The launches of both calls, on the handle's scratch between acquire and release.
+static tgms_status neighbors_on_device(tgms_handle* h, int32_t B, const int32_t* d_so, const double* dT,
+                                       const double* dC, const double* dT0, const double (&sc)[3], double r_min,
+                                       double* d_near, int32_t* d_nbr, int32_t* d_count, int32_t* d_tested,
+                                       int32_t* d_flags, hipStream_t st) {
+    tgms_status s = no_capture(h, st, "tgms_neighbors_batch_device");
+    if (s != TGMS_OK) return s;
+    TGMS_HIP(h, hipSetDevice(h->device));
+    s = ensure_nbr_ws(h, tgms::neighbors_scratch_bytes(B));
+    if (s == TGMS_OK) s = scratch_acquire(h, st);
+    if (s != TGMS_OK) return s;
+    return scratch_release(h, st, hip_err(h, tgms::launch_neighbors(B, d_so, dT, dC, dT0, sc, r_min, h->d_nbr_ws, d_near,
+                                                                    d_nbr, d_count, d_tested, d_flags, st),
+                                          "launch_neighbors"));
+}
+
+tgms_status tgms_neighbors_batch_device(tgms_handle* h, int32_t B, const int32_t* d_so, const double* dT,
+                                        const double* dC, const double* d_start_times, const double* scale,
+                                        double r_min, double* d_near, int32_t* d_nbr, int32_t* d_count,
+                                        int32_t* d_tested, int32_t* d_flags, void* stream) {
+    if (tgms_status e = enter(h, __func__); e != TGMS_OK) return e;
+    double sc[3];
+    const tgms_status s = check_neighbors(h, B, scale, r_min, d_near, d_nbr, d_count, d_flags, sc);
+    if (s != TGMS_OK) return s;
+    if (B == 0) return TGMS_OK;
+    if (!d_so || !dT || !dC) return set_err(h, TGMS_ERR_INVALID_ARG, "NULL device pointer");
+    TGMS_CHECK_ALIGNED(h, dT, dC, d_start_times, d_near);
+    return neighbors_on_device(h, B, d_so, dT, dC, d_start_times, sc, r_min, d_near, d_nbr, d_count, d_tested, d_flags,
+                               static_cast<hipStream_t>(stream));
+}
+
+tgms_status tgms_neighbors_batch(tgms_handle* h, int32_t B, const int32_t* so, const double* seg_times,
+                                 const double* coeffs, const double* start_times, const double* scale, double r_min,
+                                 double* near, int32_t* nbr, int32_t* count, int32_t* tested, int32_t* flags) {
+    if (tgms_status e = enter(h); e != TGMS_OK) return e;
+    tgms_status s = check_offsets(h, B, so, TGMS_MAX_SEGMENTS, nullptr, nullptr);
+    if (s != TGMS_OK) return s;
+    double sc[3];
+    s = check_neighbors(h, B, scale, r_min, near, nbr, count, flags, sc);
+    if (s != TGMS_OK) return s;
+    if (B == 0) return TGMS_OK;
+    if (!seg_times || !coeffs) return set_err(h, TGMS_ERR_INVALID_ARG, "NULL pointer");
+    if (h->host) {
+        tgms::host::neighbors(B, so, seg_times, coeffs, start_times, sc, r_min, near, nbr, count, tested, flags);
+        return TGMS_OK;
+    }
+    // the records first, then the four int32 rows one behind the other: one region, one download
+    const size_t S = (size_t)so[B], n = (size_t)B, rec_bytes = n * TGMS_SEP_STRIDE * sizeof(double);
+    double *dT, *dC, *dT0;
+    int32_t* dSo;
+    char* dOut;
+    s = stage(h, {input(&dT, seg_times, S), input(&dC, coeffs, S * 24), input(&dT0, start_times, n),
+                  input(&dSo, so, n + 1), output(&dOut, rec_bytes + 4 * n * sizeof(int32_t))});
+    if (s != TGMS_OK) return s;
+    double* dNear = reinterpret_cast<double*>(dOut);
+    int32_t* dI = reinterpret_cast<int32_t*>(dOut + rec_bytes);
+    s = neighbors_on_device(h, B, dSo, dT, dC, dT0, sc, r_min, dNear, dI, dI + n, dI + 2 * n, dI + 3 * n, h->stream);
+    if (s != TGMS_OK) return s;
+    std::vector<char> all(rec_bytes + 4 * n * sizeof(int32_t));
+    TGMS_HIP(h, fetch(h, all.data(), dOut, all.size()));
+    TGMS_HIP(h, hipStreamSynchronize(h->stream));
+    if (near) std::memcpy(near, all.data(), rec_bytes);
+    int32_t* const dst[4] = {nbr, count, tested, flags};
+    for (int k = 0; k < 4; ++k)
+        if (dst[k]) std::memcpy(dst[k], all.data() + rec_bytes + k * n * sizeof(int32_t), n * sizeof(int32_t));
+    return TGMS_OK;
 }
 
 // ---- multi-GPU ----

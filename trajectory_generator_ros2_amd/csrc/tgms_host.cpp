@@ -22,8 +22,11 @@
 
 #include <cfloat>
 #include <cmath>
+#include <vector>
+#include <algorithm>
 
 #include "tgms_bounds_core.h"
+#include "tgms_neighbors_core.h"
 #include "tgms_separation_core.h"
 
 namespace tgms {
@@ -376,6 +379,45 @@ int separation(int Mi, const double* ci, const double* Ti, double t0i, int Mj, c
     const int fl = sp::finish(best, at, bad, r_min, r);
     for (int q = 0; q < TGMS_SEP_STRIDE; ++q) rec[q] = r[q];
     return fl;
+}
+
+void neighbors(int32_t B, const int32_t* so, const double* T, const double* C, const double* t0, const double* scale,
+               double r_min, double* near, int32_t* nbr, int32_t* count, int32_t* tested, int32_t* flags) {
+    namespace nb = tgms::neighbors;
+    const double sc[3] = {scale[0], scale[1], scale[2]};
+    const double r2 = nb::cull_r2(r_min);
+    constexpr int BX = nb::BOXES * nb::BOX_STRIDE;
+    std::vector<int32_t> M((size_t)B);
+    std::vector<double> ub((size_t)B * nb::BOX_STRIDE), kn((size_t)B * nb::KNOT_STRIDE), bx((size_t)B * BX);
+    for (int32_t b = 0; b < B; ++b) {
+        const int m = so[b + 1] - so[b];
+        const bool ok = nb::vehicle_boxes(m, C + (int64_t)so[b] * 24, T + so[b], t0 ? t0[b] : 0.0,
+                                          &kn[(size_t)b * nb::KNOT_STRIDE], &bx[(size_t)b * BX],
+                                          &ub[(size_t)b * nb::BOX_STRIDE]);
+        M[b] = ok ? m : 0;
+    }
+    for (int32_t i = 0; i < B; ++i) {
+        nb::Row row = nb::row_init();
+        for (int32_t j = 0; j < B && M[i] > 0; ++j) {
+            if (j == i || M[j] == 0) continue;
+            if (!(nb::gap2(&ub[(size_t)i * nb::BOX_STRIDE], &ub[(size_t)j * nb::BOX_STRIDE], sc) < r2)) continue;
+            if (!nb::walk(&kn[(size_t)i * nb::KNOT_STRIDE], M[i], &bx[(size_t)i * BX], &kn[(size_t)j * nb::KNOT_STRIDE],
+                          M[j], &bx[(size_t)j * BX], sc, r2))
+                continue;
+            double rec[TGMS_SEP_STRIDE];
+            const int fl = separation(M[i], C + (int64_t)so[i] * 24, T + so[i], t0 ? t0[i] : 0.0, M[j],
+                                      C + (int64_t)so[j] * 24, T + so[j], t0 ? t0[j] : 0.0, sc, r_min, rec);
+            nb::row_update(row, j, rec, fl);
+        }
+        double rec[TGMS_SEP_STRIDE];
+        int32_t nb_i, ct;
+        const int fl = nb::row_finish(row, M[i] > 0, rec, nb_i, ct);
+        if (near) std::copy(rec, rec + TGMS_SEP_STRIDE, near + (int64_t)i * TGMS_SEP_STRIDE);
+        if (nbr) nbr[i] = nb_i;
+        if (count) count[i] = ct;
+        if (tested) tested[i] = (fl & TGMS_SEP_NONFINITE) ? 0 : row.tested;
+        if (flags) flags[i] = fl;
+    }
 }
 
 }  // namespace host

@@ -36,5 +36,13 @@ int bounds(int M, const double* coeffs, const double* seg_times, const tgms_limi
 int separation(int Mi, const double* ci, const double* Ti, double t0i, int Mj, const double* cj, const double* Tj,
                double t0j, const double* scale, double r_min, double* rec);
 
+// The swarm neighbour search (include/tgms.h tgms_neighbors_batch) of a whole batch, row by
+// row: the boxes of every vehicle once, then per row the hull test, the walk over the
+// per-segment boxes (tgms_neighbors_core.h) and separation() for what is left.  Every output
+// is nullable.
+void neighbors(int32_t B, const int32_t* seg_offsets, const double* seg_times, const double* coeffs,
+               const double* start_times, const double* scale, double r_min, double* near, int32_t* nbr,
+               int32_t* count, int32_t* tested, int32_t* flags);
+
 }  // namespace host
 }  // namespace tgms

@@ -145,4 +145,15 @@ hipError_t launch_bounds(int32_t B, const int32_t* seg_offsets, const double* T,
 hipError_t launch_separation(int32_t B, const int32_t* seg_offsets, const double* T, const double* C,
                              const double* start_times, int64_t P, const int32_t* pairs, const double (&scale)[3],
                              double r_min, double* sep, int32_t* flags, hipStream_t stream);
+
+// Swarm neighbour search (tgms_neighbors.hip): per vehicle the nearest other vehicle that comes
+// within r_min (near [B][TGMS_SEP_STRIDE], nbr [B]), how many do (count [B]), how many pairs
+// the exact computation ran for (tested [B]) and flags [B]; all nullable.  Two launches: the
+// boxes of every vehicle into `scratch` (neighbors_scratch_bytes(B), 256-byte aligned), then a
+// wavefront per tile of rows.
+size_t neighbors_scratch_bytes(int32_t B);
+hipError_t launch_neighbors(int32_t B, const int32_t* seg_offsets, const double* T, const double* C,
+                            const double* start_times, const double (&scale)[3], double r_min, void* scratch,
+                            double* near, int32_t* nbr, int32_t* count, int32_t* tested, int32_t* flags,
+                            hipStream_t stream);
 }  // namespace tgms

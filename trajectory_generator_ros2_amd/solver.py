@@ -197,6 +197,24 @@ class Solver:
             raise TgmsError(st, self.last_error())
         return sep, flags
 
+    def neighbors(self, seg_offsets, seg_times, coeffs, r_min: float, start_times=None, scale=None):
+        """Swarm neighbour search (include/tgms.h tgms_neighbors_batch): per vehicle the nearest
+        other vehicle whose closest approach is below r_min.  Returns (near [B,2] = d_min t_min,
+        nbr [B] (NEAR_NONE: nobody), count [B], tested [B], flags [B] of SEP_* bits)."""
+        so = np.ascontiguousarray(seg_offsets, dtype=np.int32)
+        T = np.ascontiguousarray(seg_times, dtype=np.float64).reshape(-1)
+        C = np.ascontiguousarray(coeffs, dtype=np.float64)
+        t0 = None if start_times is None else np.ascontiguousarray(start_times, dtype=np.float64).reshape(-1)
+        sc = None if scale is None else np.ascontiguousarray(scale, dtype=np.float64).reshape(3)
+        B = so.shape[0] - 1
+        near = np.full((B, _lib.SEP_STRIDE), np.nan, dtype=np.float64)
+        nbr, count, tested, flags = (np.full(B, -2, dtype=np.int32) for _ in range(4))
+        st = self._L.tgms_neighbors_batch(self._h, B, _ptr(so), _ptr(T), _ptr(C), _ptr(t0), _ptr(sc), float(r_min),
+                                          _ptr(near), _ptr(nbr), _ptr(count), _ptr(tested), _ptr(flags))
+        if st != _lib.OK:
+            raise TgmsError(st, self.last_error())
+        return near, nbr, count, tested, flags
+
     def refine(self, seg_offsets, waypoints, seg_times, end_derivs=None, k_T: float = 1.0, eta: float = 0.1,
                iters: int = 10, coeffs: bool = True):
         """Time-allocation refinement on the GPU (include/tgms.h tgms_refine_batch).
@@ -326,6 +344,20 @@ class Solver:
                                                   _ptr(d_coeffs), _ptr(d_start_times), int(P), _ptr(d_pairs),
                                                   _ptr(sc), float(r_min), _ptr(d_sep), _ptr(d_flags),
                                                   ctypes.c_void_p(stream))
+        if st != _lib.OK:
+            raise TgmsError(st, self.last_error())
+
+    def neighbors_device(self, B: int, d_seg_offsets, d_seg_times, d_coeffs, r_min: float, d_start_times=None,
+                         scale=None, d_near=None, d_nbr=None, d_count=None, d_tested=None, d_flags=None,
+                         stream: int = 0) -> None:
+        """tgms_neighbors_batch_device: d_near [B,2] fp64, d_nbr / d_count / d_tested / d_flags
+        [B] int32 (at least one of near, nbr, count, flags); `scale` (host, three values or
+        None) and r_min are read now.  Not capturable: it grows handle scratch with B."""
+        sc = None if scale is None else np.ascontiguousarray(scale, dtype=np.float64).reshape(3)
+        st = self._L.tgms_neighbors_batch_device(self._h, int(B), _ptr(d_seg_offsets), _ptr(d_seg_times),
+                                                 _ptr(d_coeffs), _ptr(d_start_times), _ptr(sc), float(r_min),
+                                                 _ptr(d_near), _ptr(d_nbr), _ptr(d_count), _ptr(d_tested),
+                                                 _ptr(d_flags), ctypes.c_void_p(stream))
         if st != _lib.OK:
             raise TgmsError(st, self.last_error())
 
