@@ -39,7 +39,8 @@
  *     replays may run beside uncaptured calls, but graphs holding band launches of one
  *     handle must be replayed in stream order with each other.  Calls that upload a
  *     host-side launch plan or grow scratch at call time (ragged batches,
- *     tgms_refine_loop_device, tgms_neighbors_batch_device, the multi-GPU calls, a band
+ *     tgms_refine_loop_device, tgms_neighbors_batch_device, tgms_clearance_batch_device,
+ *     the multi-GPU calls, a band
  *     capture with no slab large enough) return TGMS_ERR_UNSUPPORTED while their stream is
  *     capturing.
  *     tgms_extrema_batch_device and tgms_bounds_batch_device (one kernel, no plan, no
@@ -114,7 +115,7 @@ tgms_status tgms_create(tgms_handle** out, int device);
 /* The explicit host backend (BASELINE config 1: a ROS 2 node with no GPU; the reference
  * generates on the executor thread's CPU, src/TrajectoryGenerator.cpp:54-57, :71).  A host
  * handle runs tgms_solve_batch (reduced method), tgms_sample_batch, tgms_extrema_batch,
- * tgms_bounds_batch, tgms_separation_batch and tgms_neighbors_batch on the calling thread with the GPU path's conventions; every other entry point returns
+ * tgms_bounds_batch, tgms_separation_batch, tgms_neighbors_batch and tgms_clearance_batch on the calling thread with the GPU path's conventions; every other entry point returns
  * TGMS_ERR_UNSUPPORTED on it.  Chosen by the caller only: tgms_create never falls back to
  * it. */
 tgms_status tgms_create_host(tgms_handle** out);
@@ -402,6 +403,78 @@ tgms_status tgms_neighbors_batch_device(tgms_handle* h, int32_t B, const int32_t
 tgms_status tgms_neighbors_batch(tgms_handle* h, int32_t B, const int32_t* seg_offsets, const double* seg_times,
                                  const double* coeffs, const double* start_times, const double* scale, double r_min,
                                  double* near, int32_t* nbr, int32_t* count, int32_t* tested, int32_t* flags);
+
+/* ---- obstacle clearance: nearest static box per trajectory, far ones culled ----
+ * The step between the dynamic limits and the ranking of a sampling planner: how close does
+ * each candidate come to the pillars, shelves and net posts of the room.  The call takes the
+ * batch, K obstacles and a search horizon r_min (finite and > 0, else TGMS_ERR_INVALID_ARG).
+ *   obstacles is fp64 [K][6] = lo[3] hi[3], axis-aligned boxes in the trajectories' frame: every
+ * entry finite and lo <= hi per axis; lo == hi on an axis is allowed, which gives a plate, a
+ * rod or a point.  In the device call it is a device array, 16-byte aligned.  It may be NULL
+ * only when K == 0.  `scale` (host [3], nullable) has the meaning and the validation of the
+ * separation call.  There are no start times: the obstacles do not move.
+ *   The distance of trajectory b to obstacle k at its own time t in [0, D_b] is
+ *     d(t) = sqrt(sum_a (s_a max(lo_a - p_a(t), 0, p_a(t) - hi_a))^2),
+ * 0.0 inside the box; D_b is the left-to-right prefix sum of the trajectory's times, the
+ * `duration` of the extrema record.  d_min is the minimum of d over the closed intervals of all
+ * segments; t_min is a time in [0, D_b] at which the returned d_min is attained (a knot's
+ * prefix sum plus the local time, clamped to D_b; which one among ties is unspecified).
+ *   Per trajectory i, over all usable obstacles k:
+ *     count[i]   the number of obstacles with d_min < r_min (strict, on the stored value)
+ *     near[i]    d_min t_min of the closest of them (TGMS_SEP_STRIDE doubles)
+ *     obs[i]     its index; ties on the stored d_min go to the lowest k; TGMS_NEAR_NONE when
+ *                there is none, and then near = (+inf, 0.0)
+ *     tested[i]  the number of obstacles for which the exact computation ran
+ *     flags[i]   TGMS_SEP_CLOSE when count[i] > 0
+ * K == 0 gives every usable row the "none" result.  No result depends on the launch shape or
+ * on the order in which obstacles were processed.
+ *   Exact computation.  On a segment d^2 is C^1 and piecewise polynomial: per axis the
+ * trajectory is below the box, inside its extent or above it, and for each combination of
+ * these states d^2 is one polynomial of degree <= 14.  The minimum is the least true value at
+ * the segment ends and at the roots of the derivative of every combination the segment can be
+ * in, which the derivative ladder of the bounds call locates; the time a trajectory enters a
+ * box is such a root.  No resolution, and no cutting of the segment at the crossing times.
+ *   Culling.  That computation runs only where a conservative bound cannot rule it out: the
+ * hull of the trajectory's Bernstein boxes against the obstacle, then each segment's box, with
+ * the margin and the cull threshold of the neighbour search.  The bound is sound: an obstacle
+ * whose stored d_min would be < r_min is never culled, so count, obs and near are those of the
+ * exhaustive computation; tested makes the culling observable, with count[i] <= tested[i] <=
+ * the number of usable obstacles.
+ *   Accuracy, on the squared distance for the reason the separation block gives:
+ *     |d_min^2 - d_true^2| <= 1e-9 * L^2,
+ * L the largest scaled coordinate magnitude that the trajectory reaches or a corner of the
+ * obstacle has.  A trajectory that passes through a box therefore reports d_min <= sqrt(1e-9)
+ * L, not necessarily 0.0 to the bit (the entry time is a located root; 0.0 is exact when a
+ * segment end lies inside).  An fp64 evaluation at located candidates, not a certificate; a
+ * touch of a derivative without a sign change may be skipped.
+ *   An unusable trajectory (in the device call a segment count outside 1..TGMS_MAX_SEGMENTS,
+ * for which nothing is read; a time that is not finite and > 0; a non-finite coefficient; a
+ * non-finite result) gets TGMS_SEP_NONFINITE alone, near = NaN NaN, obs = TGMS_NEAR_NONE, count
+ * = 0 and tested = 0.  An unusable obstacle (a non-finite entry, or lo > hi on an axis) is left
+ * out of every search and sets TGMS_CLR_BAD_OBSTACLE in the flags of every usable trajectory:
+ * the rest of each row is that of the call without the obstacle, and the bit says that a wall
+ * may be missing from the answer.
+ *   At least one of near / obs / count / flags must be non-NULL; B == 0 is TGMS_OK and launches
+ * nothing.  The device call is two kernel launches on handle scratch that grows with B and K
+ * at call time (1,064 B per trajectory, 4 B per obstacle; the neighbour search's buffer),
+ * ordered among the handle's calls like all its scratch, so it returns TGMS_ERR_UNSUPPORTED
+ * while its stream is capturing.  On a multi handle it runs on device 0; on a host handle the
+ * device call returns TGMS_ERR_UNSUPPORTED and tgms_clearance_batch computes on the calling
+ * thread (the same boxes, culls and exact computation; host and device agree to the accuracy
+ * above, not to the bit); on a GPU handle it does one upload, the launches and one download. */
+#define TGMS_CLR_BAD_OBSTACLE 32 /* an unusable obstacle was left out of this row's search */
+tgms_status tgms_clearance_batch_device(tgms_handle* h, int32_t B, const int32_t* d_seg_offsets,
+                                        const double* d_seg_times, const double* d_coeffs, int32_t K,
+                                        const double* d_obstacles /* [K][6]: lo[3] hi[3] */,
+                                        const double* scale /* host [3], nullable */, double r_min,
+                                        double* d_near /* [B][TGMS_SEP_STRIDE]: d_min t_min, nullable */,
+                                        int32_t* d_obs /* [B], nullable */, int32_t* d_count /* [B], nullable */,
+                                        int32_t* d_tested /* [B], nullable */, int32_t* d_flags /* [B], nullable */,
+                                        void* stream);
+tgms_status tgms_clearance_batch(tgms_handle* h, int32_t B, const int32_t* seg_offsets, const double* seg_times,
+                                 const double* coeffs, int32_t K, const double* obstacles, const double* scale,
+                                 double r_min, double* near, int32_t* obs, int32_t* count, int32_t* tested,
+                                 int32_t* flags);
 
 /* ---- multi-GPU ----
  * One process drives devices 0 .. device_count-1 through one handle that owns one RCCL

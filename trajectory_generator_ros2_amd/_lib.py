@@ -23,6 +23,7 @@ FEAS_BOX, FEAS_SPEED, FEAS_ACCEL, FEAS_JERK, FEAS_NONFINITE = 1, 2, 4, 8, 16
 SEP_STRIDE = 2  # d_min t_min
 SEP_CLOSE, SEP_NONFINITE = 1, 16
 NEAR_NONE = -1  # tgms_neighbors_batch: nobody within r_min
+CLR_BAD_OBSTACLE = 32  # tgms_clearance_batch: an unusable obstacle was left out
 
 # Every symbol include/tgms.h declares (checked by tests/test_capi_symbols.py).
 EXPORTS = [
@@ -35,6 +36,7 @@ EXPORTS = [
     "tgms_extrema_batch", "tgms_extrema_batch_device", "tgms_bounds_batch", "tgms_bounds_batch_device",
     "tgms_separation_batch", "tgms_separation_batch_device",
     "tgms_neighbors_batch", "tgms_neighbors_batch_device",
+    "tgms_clearance_batch", "tgms_clearance_batch_device",
 ]
 
 SCHED_REFINE, SCHED_END_DERIVS, SCHED_COEFFS, SCHED_STATUS, SCHED_COST, SCHED_SELF_GATHER = 1, 2, 4, 8, 16, 32
@@ -158,6 +160,10 @@ def load(path: str = ""):
     L.tgms_neighbors_batch_device.restype = ctypes.c_int
     L.tgms_neighbors_batch.argtypes = [vp, i32, vp, vp, vp, vp, vp, dbl, vp, vp, vp, vp, vp]
     L.tgms_neighbors_batch.restype = ctypes.c_int
+    L.tgms_clearance_batch_device.argtypes = [vp, i32, vp, vp, vp, i32, vp, vp, dbl, vp, vp, vp, vp, vp, vp]
+    L.tgms_clearance_batch_device.restype = ctypes.c_int
+    L.tgms_clearance_batch.argtypes = [vp, i32, vp, vp, vp, i32, vp, vp, dbl, vp, vp, vp, vp, vp]
+    L.tgms_clearance_batch.restype = ctypes.c_int
     if L.tgms_abi_version() != ABI_VERSION:
         raise ImportError(f"libtgms ABI {L.tgms_abi_version()} != {ABI_VERSION}")
     _lib = L

@@ -63,7 +63,8 @@ struct tgms_handle {
     // blocking host API reuses)
     double* d_loop_ws = nullptr;
     size_t loop_ws_cap = 0;
-    // tgms_neighbors_batch_device's per-vehicle boxes and knots (grow-only, ordered by scratch_ev)
+    // tgms_neighbors_batch_device's per-vehicle boxes and knots, also tgms_clearance_batch_device's
+    // (grow-only, ordered by scratch_ev)
     void* d_nbr_ws = nullptr;
     size_t nbr_ws_cap = 0;
     // ragged plans: the per-M group launches fork onto these streams and join back, so
@@ -2111,6 +2112,92 @@ tgms_status tgms_neighbors_batch(tgms_handle* h, int32_t B, const int32_t* so, c
     TGMS_HIP(h, hipStreamSynchronize(h->stream));
     if (near) std::memcpy(near, all.data(), rec_bytes);
     int32_t* const dst[4] = {nbr, count, tested, flags};
+    for (int k = 0; k < 4; ++k)
+        if (dst[k]) std::memcpy(dst[k], all.data() + rec_bytes + k * n * sizeof(int32_t), n * sizeof(int32_t));
+    return TGMS_OK;
+}
+
+// ---- obstacle clearance: nearest static box per trajectory, far ones culled ----
+
+// What both calls check before they look at a pointer.
+static tgms_status check_clearance(tgms_handle* h, int32_t B, int32_t K, const double* scale, double r_min,
+                                   const void* near, const void* obs, const void* count, const void* flags,
+                                   double (&sc)[3]) {
+    if (B < 0) return set_err(h, TGMS_ERR_INVALID_ARG, "bad B");
+    if (K < 0) return set_err(h, TGMS_ERR_INVALID_ARG, "bad K");
+    if (!resolve_scale(scale, sc)) return set_err(h, TGMS_ERR_INVALID_ARG, "scale entries must be finite and > 0");
+    if (!(r_min > 0.0) || !std::isfinite(r_min)) return set_err(h, TGMS_ERR_INVALID_ARG, "r_min must be finite and > 0");
+    if (!near && !obs && !count && !flags)
+        return set_err(h, TGMS_ERR_INVALID_ARG, "near, obs, count and flags all NULL");
+    return TGMS_OK;
+}
+
+// The launches of both calls, on the handle's scratch (the neighbour search's buffer) between
+// acquire and release.
+static tgms_status clearance_on_device(tgms_handle* h, int32_t B, const int32_t* d_so, const double* dT,
+                                       const double* dC, int32_t K, const double* dOb, const double (&sc)[3],
+                                       double r_min, double* d_near, int32_t* d_obs, int32_t* d_count,
+                                       int32_t* d_tested, int32_t* d_flags, hipStream_t st) {
+    tgms_status s = no_capture(h, st, "tgms_clearance_batch_device");
+    if (s != TGMS_OK) return s;
+    TGMS_HIP(h, hipSetDevice(h->device));
+    s = ensure_nbr_ws(h, tgms::clearance_scratch_bytes(B, K));
+    if (s == TGMS_OK) s = scratch_acquire(h, st);
+    if (s != TGMS_OK) return s;
+    return scratch_release(h, st, hip_err(h, tgms::launch_clearance(B, d_so, dT, dC, K, dOb, sc, r_min, h->d_nbr_ws,
+                                                                    d_near, d_obs, d_count, d_tested, d_flags, st),
+                                          "launch_clearance"));
+}
+
+tgms_status tgms_clearance_batch_device(tgms_handle* h, int32_t B, const int32_t* d_so, const double* dT,
+                                        const double* dC, int32_t K, const double* d_obstacles, const double* scale,
+                                        double r_min, double* d_near, int32_t* d_obs, int32_t* d_count,
+                                        int32_t* d_tested, int32_t* d_flags, void* stream) {
+    if (tgms_status e = enter(h, __func__); e != TGMS_OK) return e;
+    double sc[3];
+    const tgms_status s = check_clearance(h, B, K, scale, r_min, d_near, d_obs, d_count, d_flags, sc);
+    if (s != TGMS_OK) return s;
+    if (B == 0) return TGMS_OK;
+    if (!d_so || !dT || !dC || (K > 0 && !d_obstacles)) return set_err(h, TGMS_ERR_INVALID_ARG, "NULL device pointer");
+    TGMS_CHECK_ALIGNED(h, dT, dC, d_obstacles, d_near);
+    return clearance_on_device(h, B, d_so, dT, dC, K, d_obstacles, sc, r_min, d_near, d_obs, d_count, d_tested,
+                               d_flags, static_cast<hipStream_t>(stream));
+}
+
+tgms_status tgms_clearance_batch(tgms_handle* h, int32_t B, const int32_t* so, const double* seg_times,
+                                 const double* coeffs, int32_t K, const double* obstacles, const double* scale,
+                                 double r_min, double* near, int32_t* obs, int32_t* count, int32_t* tested,
+                                 int32_t* flags) {
+    if (tgms_status e = enter(h); e != TGMS_OK) return e;
+    tgms_status s = check_offsets(h, B, so, TGMS_MAX_SEGMENTS, nullptr, nullptr);
+    if (s != TGMS_OK) return s;
+    double sc[3];
+    s = check_clearance(h, B, K, scale, r_min, near, obs, count, flags, sc);
+    if (s != TGMS_OK) return s;
+    if (B == 0) return TGMS_OK;
+    if (!seg_times || !coeffs || (K > 0 && !obstacles)) return set_err(h, TGMS_ERR_INVALID_ARG, "NULL pointer");
+    if (h->host) {
+        tgms::host::clearance(B, so, seg_times, coeffs, K, obstacles, sc, r_min, near, obs, count, tested, flags);
+        return TGMS_OK;
+    }
+    // the records first, then the four int32 rows one behind the other: one region, one download
+    const size_t S = (size_t)so[B], n = (size_t)B, rec_bytes = n * TGMS_SEP_STRIDE * sizeof(double);
+    double *dT, *dC, *dOb;
+    int32_t* dSo;
+    char* dOut;
+    s = stage(h, {input(&dT, seg_times, S), input(&dC, coeffs, S * 24), input(&dOb, obstacles, (size_t)K * 6),
+                  input(&dSo, so, n + 1), output(&dOut, rec_bytes + 4 * n * sizeof(int32_t))});
+    if (s != TGMS_OK) return s;
+    double* dNear = reinterpret_cast<double*>(dOut);
+    int32_t* dI = reinterpret_cast<int32_t*>(dOut + rec_bytes);
+    s = clearance_on_device(h, B, dSo, dT, dC, K, dOb, sc, r_min, dNear, dI, dI + n, dI + 2 * n, dI + 3 * n,
+                            h->stream);
+    if (s != TGMS_OK) return s;
+    std::vector<char> all(rec_bytes + 4 * n * sizeof(int32_t));
+    TGMS_HIP(h, fetch(h, all.data(), dOut, all.size()));
+    TGMS_HIP(h, hipStreamSynchronize(h->stream));
+    if (near) std::memcpy(near, all.data(), rec_bytes);
+    int32_t* const dst[4] = {obs, count, tested, flags};
     for (int k = 0; k < 4; ++k)
         if (dst[k]) std::memcpy(dst[k], all.data() + rec_bytes + k * n * sizeof(int32_t), n * sizeof(int32_t));
     return TGMS_OK;

@@ -26,6 +26,7 @@
 #include <algorithm>
 
 #include "tgms_bounds_core.h"
+#include "tgms_clearance_core.h"
 #include "tgms_neighbors_core.h"
 #include "tgms_separation_core.h"
 
@@ -417,6 +418,60 @@ void neighbors(int32_t B, const int32_t* so, const double* T, const double* C, c
         if (count) count[i] = ct;
         if (tested) tested[i] = (fl & TGMS_SEP_NONFINITE) ? 0 : row.tested;
         if (flags) flags[i] = fl;
+    }
+}
+
+void clearance(int32_t B, const int32_t* so, const double* T, const double* C, int32_t K, const double* obstacles,
+               const double* scale, double r_min, double* near, int32_t* obs, int32_t* count, int32_t* tested,
+               int32_t* flags) {
+    namespace nb = tgms::neighbors;
+    namespace cl = tgms::clearance;
+    namespace sp = tgms::separation;
+    const double sc[3] = {scale[0], scale[1], scale[2]};
+    const double r2 = nb::cull_r2(r_min);
+    std::vector<char> ok((size_t)K);
+    bool bad_obstacle = false;
+    for (int32_t k = 0; k < K; ++k) {
+        ok[k] = cl::obstacle_ok(obstacles + (int64_t)k * cl::OBS_STRIDE);
+        bad_obstacle = bad_obstacle || !ok[k];
+    }
+    for (int32_t i = 0; i < B; ++i) {
+        const int M = so[i + 1] - so[i];
+        const double* Ti = T + so[i];
+        const double* Ci = C + (int64_t)so[i] * 24;
+        double kn[nb::KNOT_STRIDE], bx[nb::BOXES * nb::BOX_STRIDE], ub[nb::BOX_STRIDE];
+        const bool usable = nb::vehicle_boxes(M, Ci, Ti, 0.0, kn, bx, ub);
+        nb::Row row = nb::row_init();
+        for (int32_t k = 0; k < K && usable; ++k) {
+            const double* ob = obstacles + (int64_t)k * cl::OBS_STRIDE;
+            if (!ok[k] || !(nb::gap2(ub, ob, sc) < r2)) continue;
+            double best = HUGE_VAL, at = 0.0;
+            bool bad = false, any = false;
+            for (int m = 0; m < M; ++m) {  // the kernel's items of the pair, in its order
+                const double* box = bx + (m + 1) * nb::BOX_STRIDE;
+                if (!(nb::gap2(box, ob, sc) < r2)) continue;
+                any = true;
+                const int mask = cl::admissible(box, ob);
+                const int n = cl::combo_count(mask);
+                for (int q = 0; q < n; ++q) {
+                    double d2, u;
+                    cl::combo_item(Ci + m * 24, Ti[m], ob, sc, cl::nth_combo(mask, q), d2, u);
+                    sp::fold(d2, cl::time_of(kn[m], Ti[m], u, kn[M]), best, at, bad);
+                }
+            }
+            if (!any) continue;
+            double rec[TGMS_SEP_STRIDE];
+            const int fl = sp::finish(best, at, bad, r_min, rec);
+            nb::row_update(row, k, rec, fl);
+        }
+        double rec[TGMS_SEP_STRIDE];
+        int32_t ob_i, ct;
+        const int fl = nb::row_finish(row, usable, rec, ob_i, ct);
+        if (near) std::copy(rec, rec + TGMS_SEP_STRIDE, near + (int64_t)i * TGMS_SEP_STRIDE);
+        if (obs) obs[i] = ob_i;
+        if (count) count[i] = ct;
+        if (tested) tested[i] = (fl & TGMS_SEP_NONFINITE) ? 0 : row.tested;
+        if (flags) flags[i] = cl::row_flags(fl, bad_obstacle);
     }
 }
 

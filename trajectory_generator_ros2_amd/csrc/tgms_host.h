@@ -44,5 +44,12 @@ void neighbors(int32_t B, const int32_t* seg_offsets, const double* seg_times, c
                const double* start_times, const double* scale, double r_min, double* near, int32_t* nbr,
                int32_t* count, int32_t* tested, int32_t* flags);
 
+// The obstacle clearance (include/tgms.h tgms_clearance_batch) of a whole batch, row by row: per
+// trajectory its boxes, then per usable obstacle the hull test, the segment-box test and the
+// admissible combinations of tgms_clearance_core.h for what is left.  Every output is nullable.
+void clearance(int32_t B, const int32_t* seg_offsets, const double* seg_times, const double* coeffs, int32_t K,
+               const double* obstacles, const double* scale, double r_min, double* near, int32_t* obs, int32_t* count,
+               int32_t* tested, int32_t* flags);
+
 }  // namespace host
 }  // namespace tgms

@@ -156,4 +156,15 @@ hipError_t launch_neighbors(int32_t B, const int32_t* seg_offsets, const double*
                             const double* start_times, const double (&scale)[3], double r_min, void* scratch,
                             double* near, int32_t* nbr, int32_t* count, int32_t* tested, int32_t* flags,
                             hipStream_t stream);
+
+// Obstacle clearance (tgms_clearance.hip): per trajectory the nearest of K static boxes
+// (obstacles [K][6] = lo[3] hi[3]) that comes within r_min (near [B][TGMS_SEP_STRIDE], obs [B]),
+// how many do (count [B]), how many the exact computation ran for (tested [B]) and flags [B];
+// all nullable.  Two launches: the boxes of every trajectory and a usable word per obstacle into
+// `scratch` (clearance_scratch_bytes(B, K), 256-byte aligned), then a wavefront per tile of rows.
+size_t clearance_scratch_bytes(int32_t B, int32_t K);
+hipError_t launch_clearance(int32_t B, const int32_t* seg_offsets, const double* T, const double* C, int32_t K,
+                            const double* obstacles, const double (&scale)[3], double r_min, void* scratch,
+                            double* near, int32_t* obs, int32_t* count, int32_t* tested, int32_t* flags,
+                            hipStream_t stream);
 }  // namespace tgms

@@ -215,6 +215,25 @@ class Solver:
             raise TgmsError(st, self.last_error())
         return near, nbr, count, tested, flags
 
+    def clearance(self, seg_offsets, seg_times, coeffs, obstacles, r_min: float, scale=None):
+        """Obstacle clearance (include/tgms.h tgms_clearance_batch): per trajectory the nearest of
+        the static boxes `obstacles` [K,6] = lo[3] hi[3] whose distance falls below r_min.  Returns
+        (near [B,2] = d_min t_min, obs [B] (NEAR_NONE: none), count [B], tested [B], flags [B] of
+        SEP_* bits and CLR_BAD_OBSTACLE)."""
+        so = np.ascontiguousarray(seg_offsets, dtype=np.int32)
+        T = np.ascontiguousarray(seg_times, dtype=np.float64).reshape(-1)
+        C = np.ascontiguousarray(coeffs, dtype=np.float64)
+        ob = np.ascontiguousarray(obstacles, dtype=np.float64).reshape(-1, 6)
+        sc = None if scale is None else np.ascontiguousarray(scale, dtype=np.float64).reshape(3)
+        B, K = so.shape[0] - 1, ob.shape[0]
+        near = np.full((B, _lib.SEP_STRIDE), np.nan, dtype=np.float64)
+        obs, count, tested, flags = (np.full(B, -2, dtype=np.int32) for _ in range(4))
+        st = self._L.tgms_clearance_batch(self._h, B, _ptr(so), _ptr(T), _ptr(C), K, _ptr(ob) if K else None, _ptr(sc),
+                                          float(r_min), _ptr(near), _ptr(obs), _ptr(count), _ptr(tested), _ptr(flags))
+        if st != _lib.OK:
+            raise TgmsError(st, self.last_error())
+        return near, obs, count, tested, flags
+
     def refine(self, seg_offsets, waypoints, seg_times, end_derivs=None, k_T: float = 1.0, eta: float = 0.1,
                iters: int = 10, coeffs: bool = True):
         """Time-allocation refinement on the GPU (include/tgms.h tgms_refine_batch).
@@ -357,6 +376,20 @@ class Solver:
         st = self._L.tgms_neighbors_batch_device(self._h, int(B), _ptr(d_seg_offsets), _ptr(d_seg_times),
                                                  _ptr(d_coeffs), _ptr(d_start_times), _ptr(sc), float(r_min),
                                                  _ptr(d_near), _ptr(d_nbr), _ptr(d_count), _ptr(d_tested),
+                                                 _ptr(d_flags), ctypes.c_void_p(stream))
+        if st != _lib.OK:
+            raise TgmsError(st, self.last_error())
+
+    def clearance_device(self, B: int, d_seg_offsets, d_seg_times, d_coeffs, K: int, d_obstacles, r_min: float,
+                         scale=None, d_near=None, d_obs=None, d_count=None, d_tested=None, d_flags=None,
+                         stream: int = 0) -> None:
+        """tgms_clearance_batch_device: d_obstacles [K,6] fp64, d_near [B,2] fp64, d_obs / d_count /
+        d_tested / d_flags [B] int32 (at least one of near, obs, count, flags); `scale` (host, three
+        values or None) and r_min are read now.  Not capturable: it grows handle scratch with B, K."""
+        sc = None if scale is None else np.ascontiguousarray(scale, dtype=np.float64).reshape(3)
+        st = self._L.tgms_clearance_batch_device(self._h, int(B), _ptr(d_seg_offsets), _ptr(d_seg_times),
+                                                 _ptr(d_coeffs), int(K), _ptr(d_obstacles), _ptr(sc), float(r_min),
+                                                 _ptr(d_near), _ptr(d_obs), _ptr(d_count), _ptr(d_tested),
                                                  _ptr(d_flags), ctypes.c_void_p(stream))
         if st != _lib.OK:
             raise TgmsError(st, self.last_error())
