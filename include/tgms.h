@@ -43,8 +43,8 @@
  *     the multi-GPU calls, a band
  *     capture with no slab large enough) return TGMS_ERR_UNSUPPORTED while their stream is
  *     capturing.
- *     tgms_extrema_batch_device and tgms_bounds_batch_device (one kernel, no plan, no
- *     scratch) may be captured for any batch, ragged included;
+ *     tgms_extrema_batch_device, tgms_bounds_batch_device and tgms_thrust_batch_device (one
+ *     kernel, no plan, no scratch) may be captured for any batch, ragged included;
  *   - there is no CPU fallback: with no usable GPU, tgms_create fails with
  *     TGMS_ERR_NO_DEVICE.  A GPU-less node asks for the host backend explicitly
  *     (tgms_create_host: solve + sample on the CPU, config 1).
@@ -115,7 +115,7 @@ tgms_status tgms_create(tgms_handle** out, int device);
 /* The explicit host backend (BASELINE config 1: a ROS 2 node with no GPU; the reference
  * generates on the executor thread's CPU, src/TrajectoryGenerator.cpp:54-57, :71).  A host
  * handle runs tgms_solve_batch (reduced method), tgms_sample_batch, tgms_extrema_batch,
- * tgms_bounds_batch, tgms_separation_batch, tgms_neighbors_batch and tgms_clearance_batch on the calling thread with the GPU path's conventions; every other entry point returns
+ * tgms_bounds_batch, tgms_thrust_batch, tgms_separation_batch, tgms_neighbors_batch and tgms_clearance_batch on the calling thread with the GPU path's conventions; every other entry point returns
  * TGMS_ERR_UNSUPPORTED on it.  Chosen by the caller only: tgms_create never falls back to
  * it. */
 tgms_status tgms_create_host(tgms_handle** out);
@@ -475,6 +475,72 @@ tgms_status tgms_clearance_batch(tgms_handle* h, int32_t B, const int32_t* seg_o
                                  const double* coeffs, int32_t K, const double* obstacles, const double* scale,
                                  double r_min, double* near, int32_t* obs, int32_t* count, int32_t* tested,
                                  int32_t* flags);
+
+/* ---- continuous thrust and tilt bounds from differential flatness ----
+ * Which candidates the vehicle can fly.  The dynamic limits of tgms_limits bound |p''|, but
+ * what saturates a multirotor's motors or tips it over is the mass-normalised thrust vector
+ *     f(t) = p''(t) + g e_z
+ * (differential flatness: the trajectory fixes it): 6 m/s^2 of acceleration needs 3.8 m/s^2 of
+ * thrust downwards, 15.8 upwards, and tilts the vehicle by 31 degrees sideways, and a_max
+ * passes or fails the three alike.  Per trajectory one record of TGMS_THRUST_STRIDE doubles
+ *     f_min t_fmin f_max t_fmax tilt_max t_tilt
+ * f_min / f_max the minimum and maximum of ||f|| over all segments' closed intervals (m/s^2),
+ * tilt_max the maximum of the angle between f and +z, atan2(sqrt(f_x^2 + f_y^2), f_z) in [0,
+ * pi], over the same set (radians).  Each t_* is a time in [0, D_b] at which the stored value
+ * is attained: a knot's left-to-right prefix sum of T plus the local time, clamped to D_b (the
+ * clearance call's rule); which one among ties is unspecified.
+ *   On a segment ||f||^2 is a polynomial of degree 10, and the stationary points of the tilt
+ * are the roots of f_z h' - 2 h f_z' (h = f_x^2 + f_y^2), of degree <= 13 because the leading
+ * terms cancel; the derivative ladder of the bounds call locates both.  The candidates are the
+ * segment ends and the ladders' slots, and every value is evaluated from the axis polynomials
+ * at the candidate, never from convolved coefficients: a constant trajectory gives f_min ==
+ * f_max == g to the bit and tilt_max == 0.0, a purely vertical one with f_z > 0 tilt_max ==
+ * 0.0.  O(M) work per trajectory, no resolution.
+ *   g (m/s^2) must be finite and >= 0, else TGMS_ERR_INVALID_ARG; g == 0 is allowed and gives
+ * the extremes of |p''| itself.
+ *   flags: TGMS_THRUST_* bits against `limits`, a host struct read at call time (its values
+ * travel as kernel arguments).  Strict comparisons on the very values stored; an infinite
+ * entry is unchecked; a NaN entry is TGMS_ERR_INVALID_ARG; limits == NULL checks nothing, so
+ * the flags can then carry TGMS_FEAS_NONFINITE only.  A trajectory with a non-finite
+ * coefficient, time or result, with a T_i that is not > 0 or, in the device call, with a
+ * segment count outside 1..TGMS_MAX_SEGMENTS (nothing is read for it) gets
+ * TGMS_FEAS_NONFINITE alone and an all-NaN record; its neighbours are unaffected.
+ *   Accuracy, with F the true f_max of the trajectory:
+ *     |f_min^2 - true^2| <= 1e-9 F^2,   |f_max^2 - true^2| <= 1e-9 F^2
+ * (on the squares, for the reason the separation block gives: a thrust that crosses zero
+ * reports f_min <= sqrt(1e-9) F, not necessarily 0.0), and, when f_min > 0,
+ *     |tilt_max - true| <= 1e-9 F / f_min   radians.
+ * Where the thrust vanishes on the trajectory the tilt is discontinuous: the stored tilt_max
+ * is then the maximum over the candidates and carries no accuracy claim; TGMS_THRUST_LOW is
+ * what catches such a trajectory.  fp64 evaluations at located candidates, not a certificate;
+ * a touch of a derivative without a sign change may be skipped, as for the bounds.
+ *   The body rate |f x p'''| / ||f||^2 is not computed (its stationary points are the roots of
+ * a polynomial of degree 27); j_peak / f_min from the bounds and thrust records is a sound
+ * upper bound.
+ *   At least one of rec / flags must be non-NULL; fp64 device arrays are 16-byte aligned; B == 0
+ * is TGMS_OK and launches nothing.  tgms_thrust_batch_device is one kernel launch with no host
+ * plan and no handle scratch, so it may be captured into a HIP graph for any batch, ragged
+ * included.  On a multi handle it runs on device 0; on a host handle it returns
+ * TGMS_ERR_UNSUPPORTED.  tgms_thrust_batch on a host handle computes on the calling thread
+ * (the same algorithm; host and device agree to the accuracy above, not to the bit); on a GPU
+ * handle it does one upload, the launch and one download (records and flags in one workspace
+ * region), like tgms_bounds_batch. */
+#define TGMS_THRUST_STRIDE 6 /* f_min t_fmin f_max t_fmax tilt_max t_tilt */
+#define TGMS_THRUST_LOW 1    /* f_min < limits->f_min */
+#define TGMS_THRUST_HIGH 2   /* f_max > limits->f_max */
+#define TGMS_THRUST_TILT 4   /* tilt_max > limits->tilt_max */
+/* TGMS_FEAS_NONFINITE (16) is reused */
+typedef struct tgms_thrust_limits {
+    double f_min, f_max, tilt_max;
+} tgms_thrust_limits;
+tgms_status tgms_thrust_batch_device(tgms_handle* h, int32_t B, const int32_t* d_seg_offsets,
+                                     const double* d_seg_times, const double* d_coeffs, double g,
+                                     const tgms_thrust_limits* limits /* host, nullable */,
+                                     double* d_rec /* [B][TGMS_THRUST_STRIDE], nullable */,
+                                     int32_t* d_flags /* [B], nullable */, void* stream);
+tgms_status tgms_thrust_batch(tgms_handle* h, int32_t B, const int32_t* seg_offsets,
+                              const double* seg_times, const double* coeffs, double g,
+                              const tgms_thrust_limits* limits, double* rec, int32_t* flags);
 
 /* ---- multi-GPU ----
  * One process drives devices 0 .. device_count-1 through one handle that owns one RCCL

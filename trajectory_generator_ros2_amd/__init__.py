@@ -8,11 +8,13 @@ marshals buffers for tests, the benchmark and multi-GPU sharding.
 from ._lib import (CLR_BAD_OBSTACLE, ERR_DEVICE, ERR_INVALID_ARG, ERR_NO_DEVICE, ERR_NONFINITE, ERR_SINGULAR, ERR_SKIPPED,
                    ERR_UNSUPPORTED, EXTREMA_STRIDE, FEAS_ACCEL, FEAS_BOX, FEAS_JERK, FEAS_NONFINITE, FEAS_SPEED,
                    METHOD_BAND_KKT, METHOD_DENSE_KKT, METHOD_REDUCED, NEAR_NONE, OK, SEP_CLOSE, SEP_NONFINITE, SEP_STRIDE,
-                   YAW_CONSTANT, YAW_VELOCITY, Limits, TgmsError)
+                   THRUST_HIGH, THRUST_LOW, THRUST_STRIDE, THRUST_TILT, YAW_CONSTANT, YAW_VELOCITY, Limits, TgmsError,
+                   ThrustLimits)
 
 __all__ = [
     "OK", "ERR_INVALID_ARG", "ERR_SINGULAR", "ERR_NONFINITE", "ERR_NO_DEVICE", "ERR_DEVICE",
     "ERR_UNSUPPORTED", "ERR_SKIPPED", "METHOD_REDUCED", "METHOD_DENSE_KKT", "METHOD_BAND_KKT", "YAW_CONSTANT", "YAW_VELOCITY",
     "EXTREMA_STRIDE", "FEAS_BOX", "FEAS_SPEED", "FEAS_ACCEL", "FEAS_JERK", "FEAS_NONFINITE", "Limits",
     "SEP_STRIDE", "SEP_CLOSE", "SEP_NONFINITE", "NEAR_NONE", "CLR_BAD_OBSTACLE", "TgmsError",
+    "THRUST_STRIDE", "THRUST_LOW", "THRUST_HIGH", "THRUST_TILT", "ThrustLimits",
 ]

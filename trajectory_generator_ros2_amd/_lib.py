@@ -24,6 +24,8 @@ SEP_STRIDE = 2  # d_min t_min
 SEP_CLOSE, SEP_NONFINITE = 1, 16
 NEAR_NONE = -1  # tgms_neighbors_batch: nobody within r_min
 CLR_BAD_OBSTACLE = 32  # tgms_clearance_batch: an unusable obstacle was left out
+THRUST_STRIDE = 6  # f_min t_fmin f_max t_fmax tilt_max t_tilt
+THRUST_LOW, THRUST_HIGH, THRUST_TILT = 1, 2, 4  # with FEAS_NONFINITE
 
 # Every symbol include/tgms.h declares (checked by tests/test_capi_symbols.py).
 EXPORTS = [
@@ -37,6 +39,7 @@ EXPORTS = [
     "tgms_separation_batch", "tgms_separation_batch_device",
     "tgms_neighbors_batch", "tgms_neighbors_batch_device",
     "tgms_clearance_batch", "tgms_clearance_batch_device",
+    "tgms_thrust_batch", "tgms_thrust_batch_device",
 ]
 
 SCHED_REFINE, SCHED_END_DERIVS, SCHED_COEFFS, SCHED_STATUS, SCHED_COST, SCHED_SELF_GATHER = 1, 2, 4, 8, 16, 32
@@ -66,6 +69,16 @@ class Limits(ctypes.Structure):
         self.pmin[:] = [float(x) for x in (pmin if pmin is not None else [float("-inf")] * 3)]
         self.pmax[:] = [float(x) for x in (pmax if pmax is not None else [float("inf")] * 3)]
         self.v_max, self.a_max, self.j_max = float(v_max), float(a_max), float(j_max)
+
+
+class ThrustLimits(ctypes.Structure):
+    """tgms_thrust_limits (include/tgms.h): the least and the largest mass-normalised thrust
+    (m/s^2) and the largest tilt (rad) of a thrust check.  The default checks nothing."""
+    _fields_ = [("f_min", ctypes.c_double), ("f_max", ctypes.c_double), ("tilt_max", ctypes.c_double)]
+
+    def __init__(self, f_min=float("-inf"), f_max=float("inf"), tilt_max=float("inf")):
+        super().__init__()
+        self.f_min, self.f_max, self.tilt_max = float(f_min), float(f_max), float(tilt_max)
 
 
 _lib = None
@@ -164,6 +177,10 @@ def load(path: str = ""):
     L.tgms_clearance_batch_device.restype = ctypes.c_int
     L.tgms_clearance_batch.argtypes = [vp, i32, vp, vp, vp, i32, vp, vp, dbl, vp, vp, vp, vp, vp]
     L.tgms_clearance_batch.restype = ctypes.c_int
+    L.tgms_thrust_batch_device.argtypes = [vp, i32, vp, vp, vp, dbl, ctypes.POINTER(ThrustLimits), vp, vp, vp]
+    L.tgms_thrust_batch_device.restype = ctypes.c_int
+    L.tgms_thrust_batch.argtypes = [vp, i32, vp, vp, vp, dbl, ctypes.POINTER(ThrustLimits), vp, vp]
+    L.tgms_thrust_batch.restype = ctypes.c_int
     if L.tgms_abi_version() != ABI_VERSION:
         raise ImportError(f"libtgms ABI {L.tgms_abi_version()} != {ABI_VERSION}")
     _lib = L

@@ -1949,6 +1949,68 @@ tgms_status tgms_bounds_batch(tgms_handle* h, int32_t B, const int32_t* so, cons
     return download(h, res);
 }
 
+// ---- continuous thrust and tilt bounds from differential flatness ----
+
+// The limits a launch carries: the caller's with an infinite entry of either sign turned into
+// "unchecked", or nothing checked for NULL.  A NaN entry is the caller's error.
+static bool resolve_thrust_limits(const tgms_thrust_limits* in, tgms_thrust_limits* out) {
+    const double inf = std::numeric_limits<double>::infinity();
+    *out = tgms_thrust_limits{-inf, inf, inf};
+    if (!in) return true;
+    if (std::isnan(in->f_min) || std::isnan(in->f_max) || std::isnan(in->tilt_max)) return false;
+    if (std::isfinite(in->f_min)) out->f_min = in->f_min;
+    if (std::isfinite(in->f_max)) out->f_max = in->f_max;
+    if (std::isfinite(in->tilt_max)) out->tilt_max = in->tilt_max;
+    return true;
+}
+
+tgms_status tgms_thrust_batch_device(tgms_handle* h, int32_t B, const int32_t* d_so, const double* dT,
+                                     const double* dC, double g, const tgms_thrust_limits* limits, double* d_rec,
+                                     int32_t* d_flags, void* stream) {
+    if (tgms_status e = enter(h, __func__); e != TGMS_OK) return e;
+    if (B < 0 || !(g >= 0.0) || !std::isfinite(g)) return set_err(h, TGMS_ERR_INVALID_ARG, "bad B or g");
+    tgms_thrust_limits lim;
+    if (!resolve_thrust_limits(limits, &lim)) return set_err(h, TGMS_ERR_INVALID_ARG, "NaN limit");
+    if (!d_rec && !d_flags) return set_err(h, TGMS_ERR_INVALID_ARG, "d_rec and d_flags both NULL");
+    if (B == 0) return TGMS_OK;
+    if (!d_so || !dT || !dC) return set_err(h, TGMS_ERR_INVALID_ARG, "NULL device pointer");
+    TGMS_CHECK_ALIGNED(h, dT, dC, d_rec);
+    TGMS_HIP(h, tgms::launch_thrust(B, d_so, dT, dC, g, lim, d_rec, d_flags, static_cast<hipStream_t>(stream)));
+    return TGMS_OK;
+}
+
+tgms_status tgms_thrust_batch(tgms_handle* h, int32_t B, const int32_t* so, const double* seg_times,
+                              const double* coeffs, double g, const tgms_thrust_limits* limits, double* rec,
+                              int32_t* flags) {
+    if (tgms_status e = enter(h); e != TGMS_OK) return e;
+    tgms_status s = check_offsets(h, B, so, TGMS_MAX_SEGMENTS, nullptr, nullptr);
+    if (s != TGMS_OK) return s;
+    if (!(g >= 0.0) || !std::isfinite(g)) return set_err(h, TGMS_ERR_INVALID_ARG, "bad g");
+    tgms_thrust_limits lim;
+    if (!resolve_thrust_limits(limits, &lim)) return set_err(h, TGMS_ERR_INVALID_ARG, "NaN limit");
+    if (!rec && !flags) return set_err(h, TGMS_ERR_INVALID_ARG, "rec and flags both NULL");
+    if (B == 0) return TGMS_OK;
+    if (!seg_times || !coeffs) return set_err(h, TGMS_ERR_INVALID_ARG, "NULL pointer");
+    if (h->host) {
+        for (int32_t b = 0; b < B; ++b) {
+            const int64_t s0 = so[b];
+            double r[TGMS_THRUST_STRIDE];
+            const int fl = tgms::host::thrust(so[b + 1] - so[b], coeffs + s0 * 24, seg_times + s0, g, &lim, r);
+            if (rec) std::copy(r, r + TGMS_THRUST_STRIDE, rec + (int64_t)b * TGMS_THRUST_STRIDE);
+            if (flags) flags[b] = fl;
+        }
+        return TGMS_OK;
+    }
+    const size_t S = (size_t)so[B];
+    double *dT, *dC;
+    int32_t* dSo;
+    ResultPair res{rec, flags, (size_t)B * TGMS_THRUST_STRIDE, (size_t)B};  // 48 B + 4 B per trajectory
+    s = stage(h, {input(&dT, seg_times, S), input(&dC, coeffs, S * 24), input(&dSo, so, (size_t)B + 1), output(&res)});
+    if (s != TGMS_OK) return s;
+    TGMS_HIP(h, tgms::launch_thrust(B, dSo, dT, dC, g, lim, res.d_rec(), res.d_flags(), h->stream));
+    return download(h, res);
+}
+
 // ---- continuous swarm separation: closest approach of trajectory pairs ----
 
 // The scale a launch carries: the caller's, or 1, 1, 1 for NULL.

@@ -29,6 +29,7 @@
 #include "tgms_clearance_core.h"
 #include "tgms_neighbors_core.h"
 #include "tgms_separation_core.h"
+#include "tgms_thrust_core.h"
 
 namespace tgms {
 namespace host {
@@ -336,6 +337,30 @@ int bounds(int M, const double* C, const double* T, const tgms_limits* lim, doub
     double r[TGMS_EXTREMA_STRIDE];
     const int fl = tgms::bounds::finish(lo, hi, n2, acc, bad, lim ? *lim : none, r);
     for (int q = 0; q < TGMS_EXTREMA_STRIDE; ++q) rec[q] = r[q];
+    return fl;
+}
+
+int thrust(int M, const double* C, const double* T, double g, const tgms_thrust_limits* lim, double* rec) {
+    namespace th = tgms::thrust;
+    const tgms_thrust_limits none{-HUGE_VAL, HUGE_VAL, HUGE_VAL};
+    double chk = 0.0;
+    bool bad = M < 1 || M > TGMS_MAX_SEGMENTS;
+    for (int i = 0; !bad && i < M; ++i) {
+        chk += T[i] * 0.0;
+        bad = bad || !(T[i] > 0.0);
+    }
+    for (int q = 0; !bad && q < M * 24; ++q) chk += C[q] * 0.0;
+    bad = bad || !finite(chk);
+    th::Fold f = th::fold_init();
+    for (int i = 0; !bad && i < M; ++i) {  // tgms_thrust_core.h: the kernel's items, one after the other
+        th::Item it;
+        th::thrust_item(C + i * 24, T[i], g, it);
+        th::tilt_item(C + i * 24, T[i], g, it);
+        th::fold(f, it, T[i]);
+    }
+    double r[TGMS_THRUST_STRIDE];
+    const int fl = th::finish(f, bad, lim ? *lim : none, r);
+    for (int q = 0; q < TGMS_THRUST_STRIDE; ++q) rec[q] = r[q];
     return fl;
 }
 

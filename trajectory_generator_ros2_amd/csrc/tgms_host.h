@@ -29,6 +29,14 @@ int extrema(int M, const double* coeffs, const double* seg_times, const double* 
 // algorithm is the kernel's (tgms_bounds_core.h), one item after the other.
 int bounds(int M, const double* coeffs, const double* seg_times, const tgms_limits* lim, double* rec);
 
+// The continuous thrust and tilt bounds (include/tgms.h tgms_thrust_batch) of one trajectory:
+// rec [TGMS_THRUST_STRIDE] = f_min t_fmin f_max t_fmax tilt_max t_tilt of f = p'' + g e_z;
+// returns the TGMS_THRUST_* bits against lim (nullable: nothing checked), TGMS_FEAS_NONFINITE
+// alone (rec all NaN) for an unusable trajectory.  The algorithm is the kernel's
+// (tgms_thrust_core.h), one segment after the other.
+int thrust(int M, const double* coeffs, const double* seg_times, double g, const tgms_thrust_limits* lim,
+           double* rec);
+
 // Closest approach of one pair (include/tgms.h tgms_separation_batch): trajectory i has Mi
 // segments (coeffs ci, times Ti) and starts at t0i, likewise j.  Mi or Mj == 0 says that the
 // pair's index was out of range.  rec [TGMS_SEP_STRIDE] = d_min t_min; returns the TGMS_SEP_*

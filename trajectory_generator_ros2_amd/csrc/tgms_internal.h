@@ -139,6 +139,12 @@ hipError_t launch_extrema(int32_t B, const int32_t* seg_offsets, const double* W
 hipError_t launch_bounds(int32_t B, const int32_t* seg_offsets, const double* T, const double* C,
                          const tgms_limits& lim, double* ext, int32_t* flags, hipStream_t stream);
 
+// Continuous thrust and tilt bounds (tgms_thrust.hip): per trajectory f_min t_fmin f_max t_fmax
+// tilt_max t_tilt of f = p'' + g e_z into rec [B][TGMS_THRUST_STRIDE] and flags [B] (either
+// nullable); the mapping of launch_bounds, one launch.
+hipError_t launch_thrust(int32_t B, const int32_t* seg_offsets, const double* T, const double* C, double g,
+                         const tgms_thrust_limits& lim, double* rec, int32_t* flags, hipStream_t stream);
+
 // Continuous swarm separation (tgms_separation.hip): per pair the closest approach d_min t_min
 // into sep [P][TGMS_SEP_STRIDE] and flags [P] (either nullable); pairs NULL: every unordered
 // pair, decoded on the device.  A wavefront per tile of 16 pairs, one launch.

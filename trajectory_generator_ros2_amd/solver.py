@@ -172,6 +172,23 @@ class Solver:
             raise TgmsError(st, self.last_error())
         return ext, flags
 
+    def thrust(self, seg_offsets, seg_times, coeffs, g: float = 9.80665,
+               limits: Optional[_lib.ThrustLimits] = None) -> Tuple[np.ndarray, np.ndarray]:
+        """Continuous thrust and tilt bounds (include/tgms.h tgms_thrust_batch): (rec [B,6] =
+        f_min t_fmin f_max t_fmax tilt_max t_tilt of the mass-normalised thrust p'' + g e_z,
+        flags [B] of THRUST_* bits against `limits`; None checks nothing)."""
+        so = np.ascontiguousarray(seg_offsets, dtype=np.int32)
+        T = np.ascontiguousarray(seg_times, dtype=np.float64).reshape(-1)
+        C = np.ascontiguousarray(coeffs, dtype=np.float64)
+        B = so.shape[0] - 1
+        rec = np.zeros((B, _lib.THRUST_STRIDE), dtype=np.float64)
+        flags = np.zeros(B, dtype=np.int32)
+        st = self._L.tgms_thrust_batch(self._h, B, _ptr(so), _ptr(T), _ptr(C), float(g),
+                                       None if limits is None else ctypes.byref(limits), _ptr(rec), _ptr(flags))
+        if st != _lib.OK:
+            raise TgmsError(st, self.last_error())
+        return rec, flags
+
     def separation(self, seg_offsets, seg_times, coeffs, pairs=None, start_times=None, scale=None,
                    r_min: float = 0.0) -> Tuple[np.ndarray, np.ndarray]:
         """Continuous swarm separation (include/tgms.h tgms_separation_batch): per pair the
@@ -349,6 +366,17 @@ class Solver:
         st = self._L.tgms_bounds_batch_device(self._h, int(B), _ptr(d_seg_offsets), _ptr(d_seg_times),
                                               _ptr(d_coeffs), None if limits is None else ctypes.byref(limits),
                                               _ptr(d_extrema), _ptr(d_flags), ctypes.c_void_p(stream))
+        if st != _lib.OK:
+            raise TgmsError(st, self.last_error())
+
+    def thrust_device(self, B: int, d_seg_offsets, d_seg_times, d_coeffs, g: float = 9.80665,
+                      limits: Optional[_lib.ThrustLimits] = None, d_rec=None, d_flags=None, stream: int = 0) -> None:
+        """tgms_thrust_batch_device: d_rec [B,6] fp64 and / or d_flags [B] int32 (at least
+        one); g and `limits` are read now, so they may change before the kernel runs."""
+        st = self._L.tgms_thrust_batch_device(self._h, int(B), _ptr(d_seg_offsets), _ptr(d_seg_times),
+                                              _ptr(d_coeffs), float(g),
+                                              None if limits is None else ctypes.byref(limits),
+                                              _ptr(d_rec), _ptr(d_flags), ctypes.c_void_p(stream))
         if st != _lib.OK:
             raise TgmsError(st, self.last_error())
 
