@@ -43,8 +43,9 @@
  *     the multi-GPU calls, a band
  *     capture with no slab large enough) return TGMS_ERR_UNSUPPORTED while their stream is
  *     capturing.
- *     tgms_extrema_batch_device, tgms_bounds_batch_device and tgms_thrust_batch_device (one
- *     kernel, no plan, no scratch) may be captured for any batch, ragged included;
+ *     tgms_extrema_batch_device, tgms_bounds_batch_device, tgms_thrust_batch_device and
+ *     tgms_corridor_batch_device (one kernel, no plan, no scratch) may be captured for any
+ *     batch, ragged included;
  *   - there is no CPU fallback: with no usable GPU, tgms_create fails with
  *     TGMS_ERR_NO_DEVICE.  A GPU-less node asks for the host backend explicitly
  *     (tgms_create_host: solve + sample on the CPU, config 1).
@@ -115,7 +116,7 @@ tgms_status tgms_create(tgms_handle** out, int device);
 /* The explicit host backend (BASELINE config 1: a ROS 2 node with no GPU; the reference
  * generates on the executor thread's CPU, src/TrajectoryGenerator.cpp:54-57, :71).  A host
  * handle runs tgms_solve_batch (reduced method), tgms_sample_batch, tgms_extrema_batch,
- * tgms_bounds_batch, tgms_thrust_batch, tgms_separation_batch, tgms_neighbors_batch and tgms_clearance_batch on the calling thread with the GPU path's conventions; every other entry point returns
+ * tgms_bounds_batch, tgms_thrust_batch, tgms_corridor_batch, tgms_separation_batch, tgms_neighbors_batch and tgms_clearance_batch on the calling thread with the GPU path's conventions; every other entry point returns
  * TGMS_ERR_UNSUPPORTED on it.  Chosen by the caller only: tgms_create never falls back to
  * it. */
 tgms_status tgms_create_host(tgms_handle** out);
@@ -541,6 +542,86 @@ tgms_status tgms_thrust_batch_device(tgms_handle* h, int32_t B, const int32_t* d
 tgms_status tgms_thrust_batch(tgms_handle* h, int32_t B, const int32_t* seg_offsets,
                               const double* seg_times, const double* coeffs, double g,
                               const tgms_thrust_limits* limits, double* rec, int32_t* flags);
+
+/* ---- corridor containment: worst excursion from per-segment convex polytopes ----
+ * Does each segment stay inside its safe flight corridor.  Waypoints come from a path through
+ * free space, and every leg of that path has a convex free region around it: a box, or a
+ * polytope from a decomposition.  The polynomial between two waypoints is free to bulge out of
+ * it; the planner's loop is solve, find the worst excursion per segment, insert a waypoint
+ * there, solve again.  tgms_bounds_batch tests one axis-aligned box for the whole trajectory
+ * and tgms_clearance_batch boxes to stay out of; this call takes a region per segment, with
+ * slanted faces.
+ *   faces [F][4] = n[3] d: a point p is inside a face when n . p <= d.  Segment s of the batch
+ * (s = 0 .. S-1, S = seg_offsets[B], the row of seg_times) owns the faces
+ * face_offsets[s] .. face_offsets[s+1]-1 (a CSR of faces over segments, int64), at most
+ * TGMS_COR_MAX_FACES of them.  The margin of segment s is
+ *     m_s = max over its faces h and t in [0, T_s] of  n_h . p(t) - d_h,
+ * positive: outside.  Units are the caller's: with unit normals it is a distance; nothing is
+ * normalised on the device.  A segment with no faces has m_s = -inf, time 0.0 and face
+ * TGMS_NEAR_NONE.
+ *   d_seg_rec [S][TGMS_COR_STRIDE] = m_s and the global time at which the stored value is
+ * attained: the knot's left-to-right prefix sum of T plus the local time, clamped to D_b (the
+ * clearance call's rule; which one among ties is unspecified); d_seg_face [S] the face that
+ * attains it, as an index into faces.  d_rec [B][TGMS_COR_STRIDE] = the largest m_s of the
+ * trajectory and its time, d_where [B][2] = its segment (0 .. M_b-1) and face (index into
+ * faces).  A trajectory none of whose segments has a face gets (-inf, 0.0), where = (-1, -1)
+ * and no flag.  Ties on the stored margin go to the lowest segment, then to the lowest face
+ * index: (margin, segment, face) is a total order, so no result depends on the launch shape or
+ * the processing order.
+ *   face_offsets == NULL is shared mode: all F faces apply to every segment, the flight volume
+ * as one convex polytope (a slanted net, a roof).  It requires F <= TGMS_COR_MAX_FACES, is
+ * bit-equal to the CSR call that repeats the same faces for every segment, and reports the face
+ * as the index into the F faces.
+ *   On a segment n . p(t) - d is a polynomial of degree 7; its maximum over [0, T] is the best
+ * of the two ends and the roots of a derivative of degree 6, which the derivative ladder of the
+ * bounds call locates from the segment's normalised coefficients projected onto n.  The
+ * candidates are u = 0, u = 1 and the ladder's six slots, and every value is evaluated from
+ * the three axis polynomials at the candidate -- three Horner chains, then
+ *     fma(n_z, p_z, fma(n_y, p_y, fma(n_x, p_x, -d)))
+ * -- never from the projected coefficients: a constant trajectory gives n . p0 - d with exactly
+ * that rounding, and a waypoint lying on a face gives what the end-point evaluation gives.
+ *   flags: TGMS_COR_OUTSIDE when m_max > -r, a strict comparison on the very value stored; r
+ * is the vehicle radius, or a tolerance when negative; r must be finite, else
+ * TGMS_ERR_INVALID_ARG.
+ *   Accuracy: |m - m_true| <= 1e-9 L_h, L_h = sum_a |n_a| max_t |p_a| + |d| of the winning
+ * face.  fp64 evaluations at located candidates, not a certificate; a touch of the derivative
+ * without a sign change may be skipped, as for the bounds.
+ *   Unusable inputs.  A trajectory with a non-finite coefficient, a time that is not finite and
+ * > 0, a segment whose face span is negative, larger than TGMS_COR_MAX_FACES or outside [0, F],
+ * a non-finite result or, in the device call, a segment count outside 1..TGMS_MAX_SEGMENTS
+ * gets TGMS_FEAS_NONFINITE alone, NaN records, TGMS_NEAR_NONE in where, and NaN /
+ * TGMS_NEAR_NONE in its segments' rows; its neighbours are unaffected.  For a bad segment
+ * count nothing is read (the trajectory's offsets say nothing about where its segments are),
+ * and its segments' rows are then not written at all.  An unusable face (a non-finite entry
+ * or an all-zero normal) is left out and sets TGMS_COR_BAD_FACE on every usable trajectory
+ * that owns it; the rest of the row is that of the call without the face.
+ *   At least one of the five outputs must be non-NULL; faces may be NULL only when F == 0;
+ * 0 <= F <= INT32_MAX (a face index is an int32); fp64 arrays and face_offsets are 16-byte
+ * aligned; B == 0 is TGMS_OK and launches nothing.  tgms_corridor_batch_device is one kernel
+ * launch with no host plan and no handle scratch, so it may be captured into a HIP graph for
+ * any batch.  On a multi handle it runs on device 0; on a host handle it returns
+ * TGMS_ERR_UNSUPPORTED.  tgms_corridor_batch on a host handle computes on the calling thread
+ * (the same algorithm; host and device agree to the accuracy above, not to the bit); on a GPU
+ * handle it does one upload, the launch and one download (all five results in one workspace
+ * region). */
+#define TGMS_COR_STRIDE 2      /* m_max t_max */
+#define TGMS_COR_MAX_FACES 256 /* faces of one segment at most */
+#define TGMS_COR_OUTSIDE 1     /* m_max > -r */
+#define TGMS_COR_BAD_FACE 32   /* an unusable face was left out of this row */
+/* TGMS_FEAS_NONFINITE (16) and TGMS_NEAR_NONE (-1) are reused */
+tgms_status tgms_corridor_batch_device(tgms_handle* h, int32_t B, const int32_t* d_seg_offsets,
+                                       const double* d_seg_times, const double* d_coeffs, int64_t F,
+                                       const double* d_faces /* [F][4] = n[3] d */,
+                                       const int64_t* d_face_offsets /* [S+1], S = seg_offsets[B]; NULL: all F faces apply to every segment */,
+                                       double r, double* d_rec /* [B][TGMS_COR_STRIDE], nullable */,
+                                       int32_t* d_where /* [B][2] = segment (0..M_b-1), face (index into faces), nullable */,
+                                       double* d_seg_rec /* [S][TGMS_COR_STRIDE], nullable */,
+                                       int32_t* d_seg_face /* [S], nullable */,
+                                       int32_t* d_flags /* [B], nullable */, void* stream);
+tgms_status tgms_corridor_batch(tgms_handle* h, int32_t B, const int32_t* seg_offsets, const double* seg_times,
+                                const double* coeffs, int64_t F, const double* faces, const int64_t* face_offsets,
+                                double r, double* rec, int32_t* where, double* seg_rec, int32_t* seg_face,
+                                int32_t* flags);
 
 /* ---- multi-GPU ----
  * One process drives devices 0 .. device_count-1 through one handle that owns one RCCL

@@ -5,7 +5,8 @@ The product is ``lib/libtgms.so`` (HIP kernels for gfx950 behind the C ABI in
 behind the reference's ``Trajectory`` interface.  This Python package only
 marshals buffers for tests, the benchmark and multi-GPU sharding.
 """
-from ._lib import (CLR_BAD_OBSTACLE, ERR_DEVICE, ERR_INVALID_ARG, ERR_NO_DEVICE, ERR_NONFINITE, ERR_SINGULAR, ERR_SKIPPED,
+from ._lib import (CLR_BAD_OBSTACLE, COR_BAD_FACE, COR_MAX_FACES, COR_OUTSIDE, COR_STRIDE, ERR_DEVICE, ERR_INVALID_ARG,
+                   ERR_NO_DEVICE, ERR_NONFINITE, ERR_SINGULAR, ERR_SKIPPED,
                    ERR_UNSUPPORTED, EXTREMA_STRIDE, FEAS_ACCEL, FEAS_BOX, FEAS_JERK, FEAS_NONFINITE, FEAS_SPEED,
                    METHOD_BAND_KKT, METHOD_DENSE_KKT, METHOD_REDUCED, NEAR_NONE, OK, SEP_CLOSE, SEP_NONFINITE, SEP_STRIDE,
                    THRUST_HIGH, THRUST_LOW, THRUST_STRIDE, THRUST_TILT, YAW_CONSTANT, YAW_VELOCITY, Limits, TgmsError,
@@ -17,4 +18,5 @@ __all__ = [
     "EXTREMA_STRIDE", "FEAS_BOX", "FEAS_SPEED", "FEAS_ACCEL", "FEAS_JERK", "FEAS_NONFINITE", "Limits",
     "SEP_STRIDE", "SEP_CLOSE", "SEP_NONFINITE", "NEAR_NONE", "CLR_BAD_OBSTACLE", "TgmsError",
     "THRUST_STRIDE", "THRUST_LOW", "THRUST_HIGH", "THRUST_TILT", "ThrustLimits",
+    "COR_STRIDE", "COR_MAX_FACES", "COR_OUTSIDE", "COR_BAD_FACE",
 ]

@@ -26,6 +26,9 @@ NEAR_NONE = -1  # tgms_neighbors_batch: nobody within r_min
 CLR_BAD_OBSTACLE = 32  # tgms_clearance_batch: an unusable obstacle was left out
 THRUST_STRIDE = 6  # f_min t_fmin f_max t_fmax tilt_max t_tilt
 THRUST_LOW, THRUST_HIGH, THRUST_TILT = 1, 2, 4  # with FEAS_NONFINITE
+COR_STRIDE = 2  # m_max t_max
+COR_MAX_FACES = 256  # faces of one segment at most
+COR_OUTSIDE, COR_BAD_FACE = 1, 32  # with FEAS_NONFINITE; indices use NEAR_NONE
 
 # Every symbol include/tgms.h declares (checked by tests/test_capi_symbols.py).
 EXPORTS = [
@@ -40,6 +43,7 @@ EXPORTS = [
     "tgms_neighbors_batch", "tgms_neighbors_batch_device",
     "tgms_clearance_batch", "tgms_clearance_batch_device",
     "tgms_thrust_batch", "tgms_thrust_batch_device",
+    "tgms_corridor_batch", "tgms_corridor_batch_device",
 ]
 
 SCHED_REFINE, SCHED_END_DERIVS, SCHED_COEFFS, SCHED_STATUS, SCHED_COST, SCHED_SELF_GATHER = 1, 2, 4, 8, 16, 32
@@ -181,6 +185,10 @@ def load(path: str = ""):
     L.tgms_thrust_batch_device.restype = ctypes.c_int
     L.tgms_thrust_batch.argtypes = [vp, i32, vp, vp, vp, dbl, ctypes.POINTER(ThrustLimits), vp, vp]
     L.tgms_thrust_batch.restype = ctypes.c_int
+    L.tgms_corridor_batch_device.argtypes = [vp, i32, vp, vp, vp, ctypes.c_int64, vp, vp, dbl, vp, vp, vp, vp, vp, vp]
+    L.tgms_corridor_batch_device.restype = ctypes.c_int
+    L.tgms_corridor_batch.argtypes = [vp, i32, vp, vp, vp, ctypes.c_int64, vp, vp, dbl, vp, vp, vp, vp, vp]
+    L.tgms_corridor_batch.restype = ctypes.c_int
     if L.tgms_abi_version() != ABI_VERSION:
         raise ImportError(f"libtgms ABI {L.tgms_abi_version()} != {ABI_VERSION}")
     _lib = L

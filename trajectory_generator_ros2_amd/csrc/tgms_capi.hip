@@ -2011,6 +2011,81 @@ tgms_status tgms_thrust_batch(tgms_handle* h, int32_t B, const int32_t* so, cons
     return download(h, res);
 }
 
+// ---- corridor containment: worst excursion from per-segment polytopes ----
+
+// The argument rules the two corridor entry points share (include/tgms.h).
+static tgms_status check_corridor(tgms_handle* h, int32_t B, int64_t F, const void* faces, const void* face_offsets,
+                                  double r, const void* rec, const void* where, const void* seg_rec,
+                                  const void* seg_face, const void* flags) {
+    if (B < 0 || F < 0 || F > INT32_MAX) return set_err(h, TGMS_ERR_INVALID_ARG, "bad B or F");
+    if (!std::isfinite(r)) return set_err(h, TGMS_ERR_INVALID_ARG, "r is not finite");
+    if (!rec && !where && !seg_rec && !seg_face && !flags) return set_err(h, TGMS_ERR_INVALID_ARG, "every output is NULL");
+    if (F > 0 && !faces) return set_err(h, TGMS_ERR_INVALID_ARG, "faces is NULL with F > 0");
+    if (!face_offsets && F > TGMS_COR_MAX_FACES)
+        return set_err(h, TGMS_ERR_INVALID_ARG, "shared faces: F > TGMS_COR_MAX_FACES");
+    return TGMS_OK;
+}
+
+tgms_status tgms_corridor_batch_device(tgms_handle* h, int32_t B, const int32_t* d_so, const double* dT,
+                                       const double* dC, int64_t F, const double* d_faces,
+                                       const int64_t* d_face_offsets, double r, double* d_rec, int32_t* d_where,
+                                       double* d_seg_rec, int32_t* d_seg_face, int32_t* d_flags, void* stream) {
+    if (tgms_status e = enter(h, __func__); e != TGMS_OK) return e;
+    const tgms_status s = check_corridor(h, B, F, d_faces, d_face_offsets, r, d_rec, d_where, d_seg_rec, d_seg_face, d_flags);
+    if (s != TGMS_OK) return s;
+    if (B == 0) return TGMS_OK;
+    if (!d_so || !dT || !dC) return set_err(h, TGMS_ERR_INVALID_ARG, "NULL device pointer");
+    TGMS_CHECK_ALIGNED(h, dT, dC, d_faces, d_face_offsets, d_rec, d_seg_rec);
+    TGMS_HIP(h, tgms::launch_corridor(B, d_so, dT, dC, F, d_faces, d_face_offsets, r, d_rec, d_where, d_seg_rec,
+                                      d_seg_face, d_flags, static_cast<hipStream_t>(stream)));
+    return TGMS_OK;
+}
+
+tgms_status tgms_corridor_batch(tgms_handle* h, int32_t B, const int32_t* so, const double* seg_times,
+                                const double* coeffs, int64_t F, const double* faces, const int64_t* face_offsets,
+                                double r, double* rec, int32_t* where, double* seg_rec, int32_t* seg_face,
+                                int32_t* flags) {
+    if (tgms_status e = enter(h); e != TGMS_OK) return e;
+    tgms_status s = check_offsets(h, B, so, TGMS_MAX_SEGMENTS, nullptr, nullptr);
+    if (s != TGMS_OK) return s;
+    s = check_corridor(h, B, F, faces, face_offsets, r, rec, where, seg_rec, seg_face, flags);
+    if (s != TGMS_OK) return s;
+    if (B == 0) return TGMS_OK;
+    if (!seg_times || !coeffs) return set_err(h, TGMS_ERR_INVALID_ARG, "NULL pointer");
+    if (h->host) {
+        tgms::host::corridor(B, so, seg_times, coeffs, F, faces, face_offsets, r, rec, where, seg_rec, seg_face, flags);
+        return TGMS_OK;
+    }
+    // the fp64 rows first (per segment, then per trajectory), then the int32 rows one behind the
+    // other: one region, one download
+    const size_t S = (size_t)so[B], n = (size_t)B;
+    const size_t seg_bytes = S * TGMS_COR_STRIDE * sizeof(double), rec_bytes = n * TGMS_COR_STRIDE * sizeof(double);
+    const size_t all_bytes = seg_bytes + rec_bytes + (S + 3 * n) * sizeof(int32_t);
+    double *dT, *dC, *dF;
+    int64_t* dFo;
+    int32_t* dSo;
+    char* dOut;
+    s = stage(h, {input(&dT, seg_times, S), input(&dC, coeffs, S * 24), input(&dF, faces, (size_t)F * 4),
+                  input(&dFo, face_offsets, S + 1), input(&dSo, so, n + 1), output(&dOut, all_bytes)});
+    if (s != TGMS_OK) return s;
+    double* dSegRec = reinterpret_cast<double*>(dOut);
+    double* dRec = reinterpret_cast<double*>(dOut + seg_bytes);
+    int32_t* dI = reinterpret_cast<int32_t*>(dOut + seg_bytes + rec_bytes);  // seg_face [S], where [B][2], flags [B]
+    TGMS_HIP(h, tgms::launch_corridor(B, dSo, dT, dC, F, dF, dFo, r, dRec, dI + S, dSegRec, dI, dI + S + 2 * n,
+                                      h->stream));
+    std::vector<char> all(all_bytes);
+    TGMS_HIP(h, fetch(h, all.data(), dOut, all.size()));
+    TGMS_HIP(h, hipStreamSynchronize(h->stream));
+    const char* p = all.data();
+    if (seg_rec) std::memcpy(seg_rec, p, seg_bytes);
+    if (rec) std::memcpy(rec, p + seg_bytes, rec_bytes);
+    p += seg_bytes + rec_bytes;
+    if (seg_face) std::memcpy(seg_face, p, S * sizeof(int32_t));
+    if (where) std::memcpy(where, p + S * sizeof(int32_t), 2 * n * sizeof(int32_t));
+    if (flags) std::memcpy(flags, p + (S + 2 * n) * sizeof(int32_t), n * sizeof(int32_t));
+    return TGMS_OK;
+}
+
 // ---- continuous swarm separation: closest approach of trajectory pairs ----
 
 // The scale a launch carries: the caller's, or 1, 1, 1 for NULL.

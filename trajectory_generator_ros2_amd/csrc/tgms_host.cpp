@@ -27,6 +27,7 @@
 
 #include "tgms_bounds_core.h"
 #include "tgms_clearance_core.h"
+#include "tgms_corridor_core.h"
 #include "tgms_neighbors_core.h"
 #include "tgms_separation_core.h"
 #include "tgms_thrust_core.h"
@@ -497,6 +498,71 @@ void clearance(int32_t B, const int32_t* so, const double* T, const double* C, i
         if (count) count[i] = ct;
         if (tested) tested[i] = (fl & TGMS_SEP_NONFINITE) ? 0 : row.tested;
         if (flags) flags[i] = cl::row_flags(fl, bad_obstacle);
+    }
+}
+
+void corridor(int32_t B, const int32_t* so, const double* T, const double* C, int64_t F, const double* faces,
+              const int64_t* fo, double r, double* rec, int32_t* where, double* seg_rec, int32_t* seg_face,
+              int32_t* flags) {
+    namespace co = tgms::corridor;
+    for (int32_t b = 0; b < B; ++b) {
+        const int64_t s0 = so[b];
+        const int M = so[b + 1] - so[b];
+        const double* Tb = T + s0;
+        const double* Cb = C + s0 * 24;
+        double chk = 0.0;
+        bool bad = M < 1 || M > TGMS_MAX_SEGMENTS;
+        for (int i = 0; !bad && i < M; ++i) {
+            chk += Tb[i] * 0.0;
+            bad = bad || !(Tb[i] > 0.0);
+        }
+        for (int q = 0; !bad && q < M * 24; ++q) chk += Cb[q] * 0.0;
+        bad = bad || !finite(chk);
+        for (int i = 0; !bad && i < M; ++i) bad = !co::span_ok(fo ? fo[s0 + i] : 0, fo ? fo[s0 + i + 1] : F, F);
+        if (M < 1 || M > TGMS_MAX_SEGMENTS) {  // nothing is read, and no segment row is written
+            if (rec) rec[(int64_t)b * 2] = rec[(int64_t)b * 2 + 1] = __builtin_nan("");
+            if (where) where[(int64_t)b * 2] = where[(int64_t)b * 2 + 1] = TGMS_NEAR_NONE;
+            if (flags) flags[b] = TGMS_FEAS_NONFINITE;
+            continue;
+        }
+        // tgms_corridor_core.h: the kernel's items, one after the other
+        co::SegBest best[TGMS_MAX_SEGMENTS];
+        double kn[TGMS_MAX_SEGMENTS];
+        co::Fold f = co::fold_init();
+        bool bad_face = false;
+        for (int i = 0; i < M; ++i) {
+            best[i] = co::seg_init();
+            const int64_t fb = fo ? fo[s0 + i] : 0, fe = fo ? fo[s0 + i + 1] : F;
+            for (int64_t h = fb; !bad && h < fe; ++h) {
+                const double* n = faces + h * 4;
+                if (!co::face_ok(n[0], n[1], n[2], n[3])) {
+                    bad_face = true;
+                    continue;
+                }
+                double m, u;
+                co::item(Cb + i * 24, Tb[i], n[0], n[1], n[2], n[3], m, u);
+                co::seg_take(best[i], m, u, (int32_t)h);
+            }
+            kn[i] = f.next;
+            co::fold(f, best[i], i, Tb[i]);
+        }
+        double out[TGMS_COR_STRIDE];
+        int32_t wh[2];
+        const int fl = co::finish(f, bad, bad_face, r, out, wh);
+        bad = (fl & TGMS_FEAS_NONFINITE) != 0;
+        if (rec) std::copy(out, out + TGMS_COR_STRIDE, rec + (int64_t)b * TGMS_COR_STRIDE);
+        if (where) std::copy(wh, wh + 2, where + (int64_t)b * 2);
+        if (flags) flags[b] = fl;
+        for (int i = 0; i < M && (seg_rec || seg_face); ++i) {
+            double m, t;
+            int32_t face;
+            co::seg_row(best[i], kn[i], Tb[i], f.next, bad, m, t, face);
+            if (seg_rec) {
+                seg_rec[(s0 + i) * TGMS_COR_STRIDE] = m;
+                seg_rec[(s0 + i) * TGMS_COR_STRIDE + 1] = t;
+            }
+            if (seg_face) seg_face[s0 + i] = face;
+        }
     }
 }
 

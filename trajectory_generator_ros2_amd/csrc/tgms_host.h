@@ -59,5 +59,13 @@ void clearance(int32_t B, const int32_t* seg_offsets, const double* seg_times, c
                const double* obstacles, const double* scale, double r_min, double* near, int32_t* obs, int32_t* count,
                int32_t* tested, int32_t* flags);
 
+// The corridor containment (include/tgms.h tgms_corridor_batch) of a whole batch, trajectory by
+// trajectory: per segment and face the item of tgms_corridor_core.h, the segment's fold in face
+// order, the trajectory's fold left to right.  face_offsets NULL: all F faces apply to every
+// segment.  Every output is nullable.
+void corridor(int32_t B, const int32_t* seg_offsets, const double* seg_times, const double* coeffs, int64_t F,
+              const double* faces, const int64_t* face_offsets, double r, double* rec, int32_t* where,
+              double* seg_rec, int32_t* seg_face, int32_t* flags);
+
 }  // namespace host
 }  // namespace tgms

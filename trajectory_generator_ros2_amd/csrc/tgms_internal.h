@@ -145,6 +145,15 @@ hipError_t launch_bounds(int32_t B, const int32_t* seg_offsets, const double* T,
 hipError_t launch_thrust(int32_t B, const int32_t* seg_offsets, const double* T, const double* C, double g,
                          const tgms_thrust_limits& lim, double* rec, int32_t* flags, hipStream_t stream);
 
+// Corridor containment (tgms_corridor.hip): per trajectory m_max t_max into rec
+// [B][TGMS_COR_STRIDE], its segment and face into where [B][2], per segment m_s t_s into
+// seg_rec [S][TGMS_COR_STRIDE] and its face into seg_face [S], flags [B] (each nullable);
+// face_offsets NULL: all F <= TGMS_COR_MAX_FACES faces apply to every segment.  The tile of
+// launch_bounds with the (segment, face) item as the unit of lane work, one launch.
+hipError_t launch_corridor(int32_t B, const int32_t* seg_offsets, const double* T, const double* C, int64_t F,
+                           const double* faces, const int64_t* face_offsets, double r, double* rec, int32_t* where,
+                           double* seg_rec, int32_t* seg_face, int32_t* flags, hipStream_t stream);
+
 // Continuous swarm separation (tgms_separation.hip): per pair the closest approach d_min t_min
 // into sep [P][TGMS_SEP_STRIDE] and flags [P] (either nullable); pairs NULL: every unordered
 // pair, decoded on the device.  A wavefront per tile of 16 pairs, one launch.

@@ -189,6 +189,30 @@ class Solver:
             raise TgmsError(st, self.last_error())
         return rec, flags
 
+    def corridor(self, seg_offsets, seg_times, coeffs, faces, face_offsets=None, r: float = 0.0):
+        """Corridor containment (include/tgms.h tgms_corridor_batch): faces [F,4] = n[3] d, a point
+        inside when n . p <= d; face_offsets [S+1] int64 gives each segment its faces, None
+        applies all F (at most COR_MAX_FACES) to every segment.  Returns (rec [B,2] = m_max
+        t_max, where [B,2] = segment, face, seg_rec [S,2] = m_s t_s, seg_face [S], flags [B] of
+        COR_* bits; COR_OUTSIDE when m_max > -r)."""
+        so = np.ascontiguousarray(seg_offsets, dtype=np.int32)
+        T = np.ascontiguousarray(seg_times, dtype=np.float64).reshape(-1)
+        C = np.ascontiguousarray(coeffs, dtype=np.float64)
+        fc = np.ascontiguousarray(faces, dtype=np.float64).reshape(-1, 4)
+        fo = None if face_offsets is None else np.ascontiguousarray(face_offsets, dtype=np.int64)
+        B, S = so.shape[0] - 1, int(so[-1])
+        rec = np.zeros((B, _lib.COR_STRIDE), dtype=np.float64)
+        where = np.zeros((B, 2), dtype=np.int32)
+        seg_rec = np.zeros((S, _lib.COR_STRIDE), dtype=np.float64)
+        seg_face = np.zeros(S, dtype=np.int32)
+        flags = np.zeros(B, dtype=np.int32)
+        st = self._L.tgms_corridor_batch(self._h, B, _ptr(so), _ptr(T), _ptr(C), fc.shape[0],
+                                         _ptr(fc) if fc.shape[0] else None, _ptr(fo), float(r), _ptr(rec),
+                                         _ptr(where), _ptr(seg_rec), _ptr(seg_face), _ptr(flags))
+        if st != _lib.OK:
+            raise TgmsError(st, self.last_error())
+        return rec, where, seg_rec, seg_face, flags
+
     def separation(self, seg_offsets, seg_times, coeffs, pairs=None, start_times=None, scale=None,
                    r_min: float = 0.0) -> Tuple[np.ndarray, np.ndarray]:
         """Continuous swarm separation (include/tgms.h tgms_separation_batch): per pair the
@@ -377,6 +401,19 @@ class Solver:
                                               _ptr(d_coeffs), float(g),
                                               None if limits is None else ctypes.byref(limits),
                                               _ptr(d_rec), _ptr(d_flags), ctypes.c_void_p(stream))
+        if st != _lib.OK:
+            raise TgmsError(st, self.last_error())
+
+    def corridor_device(self, B: int, d_seg_offsets, d_seg_times, d_coeffs, F: int, d_faces, d_face_offsets=None,
+                        r: float = 0.0, d_rec=None, d_where=None, d_seg_rec=None, d_seg_face=None, d_flags=None,
+                        stream: int = 0) -> None:
+        """tgms_corridor_batch_device: d_faces [F,4] fp64, d_face_offsets [S+1] int64 or None (all
+        F faces apply to every segment); d_rec [B,2] fp64, d_where [B,2] int32, d_seg_rec [S,2]
+        fp64, d_seg_face [S] int32, d_flags [B] int32 (at least one)."""
+        st = self._L.tgms_corridor_batch_device(self._h, int(B), _ptr(d_seg_offsets), _ptr(d_seg_times),
+                                                _ptr(d_coeffs), int(F), _ptr(d_faces), _ptr(d_face_offsets),
+                                                float(r), _ptr(d_rec), _ptr(d_where), _ptr(d_seg_rec),
+                                                _ptr(d_seg_face), _ptr(d_flags), ctypes.c_void_p(stream))
         if st != _lib.OK:
             raise TgmsError(st, self.last_error())
 

@@ -50,3 +50,22 @@ def ragged_batch(B: int, m_lo: int = 2, m_hi: int = 16, seed: int = SEED):
     rows = np.arange(S) + np.repeat(np.arange(B), Ms)
     T = np.clip(np.linalg.norm(W[rows + 1] - W[rows], axis=1) / V_NOMINAL, T_MIN, T_MAX)
     return so.astype(np.int32), W, T
+
+
+def box_corridor(seg_offsets, waypoints, width: float):
+    """The simplest corridor of a batch: per segment the bounding box of its two waypoints grown
+    by `width` on every side, as six axis-aligned faces +x -x +y -y +z -z (n[3] d, inside when
+    n . p <= d).  waypoints [S+B,3] in CSR order (segment i of trajectory b joins rows
+    seg_offsets[b] + b + i and + 1; a [B,M+1,3] array reshapes to it).  Returns (faces [6S,4]
+    float64, face_offsets [S+1] int64) for tgms_corridor_batch."""
+    so = np.asarray(seg_offsets, dtype=np.int64)
+    W = np.asarray(waypoints, dtype=np.float64).reshape(-1, 3)
+    S = int(so[-1])
+    rows = np.arange(S) + np.repeat(np.arange(len(so) - 1), np.diff(so))
+    lo = np.minimum(W[rows], W[rows + 1]) - width
+    hi = np.maximum(W[rows], W[rows + 1]) + width
+    faces = np.zeros((S, 6, 4), dtype=np.float64)
+    for ax in range(3):
+        faces[:, 2 * ax, ax], faces[:, 2 * ax, 3] = 1.0, hi[:, ax]
+        faces[:, 2 * ax + 1, ax], faces[:, 2 * ax + 1, 3] = -1.0, -lo[:, ax]
+    return faces.reshape(-1, 4), 6 * np.arange(S + 1, dtype=np.int64)
