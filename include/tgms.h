@@ -40,7 +40,7 @@
  *     handle must be replayed in stream order with each other.  Calls that upload a
  *     host-side launch plan or grow scratch at call time (ragged batches,
  *     tgms_refine_loop_device, tgms_neighbors_batch_device, tgms_clearance_batch_device,
- *     the multi-GPU calls, a band
+ *     tgms_corridor_split_batch_device, the multi-GPU calls, a band
  *     capture with no slab large enough) return TGMS_ERR_UNSUPPORTED while their stream is
  *     capturing.
  *     tgms_extrema_batch_device, tgms_bounds_batch_device, tgms_thrust_batch_device and
@@ -116,7 +116,7 @@ tgms_status tgms_create(tgms_handle** out, int device);
 /* The explicit host backend (BASELINE config 1: a ROS 2 node with no GPU; the reference
  * generates on the executor thread's CPU, src/TrajectoryGenerator.cpp:54-57, :71).  A host
  * handle runs tgms_solve_batch (reduced method), tgms_sample_batch, tgms_extrema_batch,
- * tgms_bounds_batch, tgms_thrust_batch, tgms_corridor_batch, tgms_separation_batch, tgms_neighbors_batch and tgms_clearance_batch on the calling thread with the GPU path's conventions; every other entry point returns
+ * tgms_bounds_batch, tgms_thrust_batch, tgms_corridor_batch, tgms_corridor_split_batch, tgms_separation_batch, tgms_neighbors_batch and tgms_clearance_batch on the calling thread with the GPU path's conventions; every other entry point returns
  * TGMS_ERR_UNSUPPORTED on it.  Chosen by the caller only: tgms_create never falls back to
  * it. */
 tgms_status tgms_create_host(tgms_handle** out);
@@ -622,6 +622,94 @@ tgms_status tgms_corridor_batch(tgms_handle* h, int32_t B, const int32_t* seg_of
                                 const double* coeffs, int64_t F, const double* faces, const int64_t* face_offsets,
                                 double r, double* rec, int32_t* where, double* seg_rec, int32_t* seg_face,
                                 int32_t* flags);
+
+/* ---- corridor split: insert waypoints at the worst excursions ----
+ * The third step of the planner's loop (solve, find the worst excursion per segment, insert a
+ * waypoint there, solve again), on the results of one tgms_corridor_batch call: d_seg_rec and
+ * d_seg_face are that call's, with the same faces, face_offsets and r.  The call rebuilds the
+ * batch -- seg_offsets, waypoints, seg_times and the CSR of faces -- with the new waypoints in
+ * place, ready for the next solve.  The caller sizes the outputs for the most the call can
+ * produce, 2 S segments (S = seg_offsets[B]) and 2 F faces: d_seg_offsets_out [B+1],
+ * d_waypoints_out [2S+B][3], d_seg_times_out [2S], d_faces_out [2F][4], d_face_offsets_out
+ * [2S+1], d_parent [2S]; d_totals [2] receives S' and F', the rows that were written.
+ *   Which segments are split.  Segment s of a usable trajectory is wanted when m_s > -r, the
+ * corridor flag's comparison: strict, on the stored d_seg_rec[s][0]; -inf (no faces) is never
+ * wanted.  Its local time is t_loc = min(max(t_s - knot_s, 0), T_s), knot_s the left-to-right
+ * prefix sum of T that the corridor call uses.  A wanted segment with t_loc <= 2^-20 T_s or
+ * t_loc >= (1 - 2^-20) T_s is not split and sets TGMS_SPLIT_AT_END: its worst excursion is at a
+ * waypoint, which no inserted waypoint repairs (and t_s - knot_s is not exact to the bit at the
+ * right end).  Of the w wanted segments that remain in a trajectory of M_b segments the first
+ * min(w, TGMS_MAX_SEGMENTS - M_b) are split, in the order larger m_s, then lower segment; one
+ * that is dropped sets TGMS_SPLIT_FULL.  TGMS_SPLIT_DONE says that at least one was split.
+ *   Times.  lo = min_frac T_s, hi = T_s - lo, T_left = min(max(t_loc, lo), hi), T_right = T_s -
+ * T_left, every operation rounded on its own (no fused multiply-add): the times are specified to
+ * the bit and are the same on the device, on the host backend and in any fp64 re-computation.
+ * min_frac must be finite, > 0 and <= 0.5.
+ *   The inserted waypoint.  TGMS_SPLIT_PULL: x = p(T_left) from the three axis Horner chains of
+ * the segment's coefficients, q = fma(n_z, x_z, fma(n_y, x_y, fma(n_x, x_x, -d))) for face
+ * d_seg_face[s]; where q > -r the point is x - ((q + r) / (n . n)) n, else x.  Nothing assumes
+ * unit normals.  The point then has margin -r against that one face and nothing is promised
+ * about the others.  TGMS_SPLIT_CHORD: w_i + (T_left / T_s) (w_i+1 - w_i) from the input
+ * waypoints; by convexity it is inside every face that both waypoints are inside, so this mode
+ * guarantees containment of the new waypoint and PULL stays closer to the solved path.
+ *   Copied data.  The original waypoints and the times of unsplit segments are copied bit for
+ * bit.  end_derivs apply to a trajectory's two ends, which do not move: they stay valid as they
+ * are and are not an argument.
+ *   Faces.  CSR mode: the output lists the segments in their new order; each child of a split
+ * segment owns its own copy of the parent's span, in the parent's order (a CSR cannot share a
+ * span: face_offsets[s+1] is an end and a start).  d_parent[s'] is the input segment row that
+ * s' came from, so a caller can carry its own per-segment data.  Shared mode (d_face_offsets
+ * NULL): d_faces_out and d_face_offsets_out must be NULL and F' = F.
+ *   Unusable trajectories.  A trajectory with a non-finite coefficient, time or waypoint, a
+ * time that is not > 0, a NaN in one of its d_seg_rec rows, a d_seg_face outside its segment's
+ * span while the segment is wanted, or a face span that the corridor call rejects is copied
+ * through unchanged with TGMS_FEAS_NONFINITE alone; a span that cannot be used owns no face
+ * afterwards.  In the device call a segment count outside 1..TGMS_MAX_SEGMENTS means that
+ * nothing can be read for the trajectory: it becomes one placeholder segment with a NaN time,
+ * two NaN waypoints, parent TGMS_NEAR_NONE and no faces, so that the output stays a valid CSR
+ * and the solve that follows reports TGMS_ERR_INVALID_ARG for that row alone; its neighbours are
+ * unaffected.  Only such offsets can make the output exceed the capacities above; rows beyond
+ * them are then not written, so no write lands outside a buffer.
+ *   No result depends on the launch shape, and a repeated call gives the same bits.  The host
+ * backend's integers and times are the device's to the bit; inserted waypoints agree to 1e-9 of
+ * max |p| over the segment.
+ *   d_parent and d_flags are nullable.  The fp64 and int64 arrays are 16-byte aligned; mode
+ * outside the two above, a non-finite r or a bad min_frac is TGMS_ERR_INVALID_ARG; B == 0 is
+ * TGMS_OK, writes d_seg_offsets_out[0] = 0 and d_totals = (0, 0 or, in shared mode, F) and
+ * nothing else.  The device call runs five launches on `stream` (plan, three for the prefix
+ * sums, write) on handle scratch that grows with B: like tgms_neighbors_batch_device it returns
+ * TGMS_ERR_UNSUPPORTED while its stream is capturing and is ordered among the handle's other
+ * scratch users.  On a multi handle it runs on device 0; on a host handle it returns
+ * TGMS_ERR_UNSUPPORTED.  tgms_corridor_split_batch on a host handle computes on the calling
+ * thread; on a GPU handle it does one upload, the launches and one download, and copies the
+ * first S' / F' rows to the caller. */
+#define TGMS_SPLIT_PULL 0   /* p(t) moved back along -n of the segment's worst face to margin -r */
+#define TGMS_SPLIT_CHORD 1  /* the point of the straight line between the segment's two waypoints at the same fraction */
+#define TGMS_SPLIT_DONE 1   /* at least one segment of this trajectory was split */
+#define TGMS_SPLIT_FULL 2   /* a wanted split was dropped: M would exceed TGMS_MAX_SEGMENTS */
+#define TGMS_SPLIT_AT_END 4 /* a flagged segment's worst excursion is at a waypoint: not split */
+/* TGMS_FEAS_NONFINITE (16) is reused */
+tgms_status tgms_corridor_split_batch_device(tgms_handle* h, int32_t B, const int32_t* d_seg_offsets,
+                                             const double* d_waypoints, const double* d_seg_times,
+                                             const double* d_coeffs, int64_t F, const double* d_faces,
+                                             const int64_t* d_face_offsets /* NULL: shared mode */,
+                                             const double* d_seg_rec /* [S][2] of the corridor call */,
+                                             const int32_t* d_seg_face /* [S] */, double r, int mode,
+                                             double min_frac, int32_t* d_seg_offsets_out /* [B+1] */,
+                                             double* d_waypoints_out /* [2S+B][3] */,
+                                             double* d_seg_times_out /* [2S] */,
+                                             double* d_faces_out /* [2F][4], NULL in shared mode */,
+                                             int64_t* d_face_offsets_out /* [2S+1], NULL in shared mode */,
+                                             int32_t* d_parent /* [2S], nullable */,
+                                             int64_t* d_totals /* [2]: S', F' */,
+                                             int32_t* d_flags /* [B], nullable */, void* stream);
+tgms_status tgms_corridor_split_batch(tgms_handle* h, int32_t B, const int32_t* seg_offsets,
+                                      const double* waypoints, const double* seg_times, const double* coeffs,
+                                      int64_t F, const double* faces, const int64_t* face_offsets,
+                                      const double* seg_rec, const int32_t* seg_face, double r, int mode,
+                                      double min_frac, int32_t* seg_offsets_out, double* waypoints_out,
+                                      double* seg_times_out, double* faces_out, int64_t* face_offsets_out,
+                                      int32_t* parent, int64_t* totals, int32_t* flags);
 
 /* ---- multi-GPU ----
  * One process drives devices 0 .. device_count-1 through one handle that owns one RCCL

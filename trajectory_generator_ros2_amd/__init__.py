@@ -9,7 +9,8 @@ from ._lib import (CLR_BAD_OBSTACLE, COR_BAD_FACE, COR_MAX_FACES, COR_OUTSIDE, C
                    ERR_NO_DEVICE, ERR_NONFINITE, ERR_SINGULAR, ERR_SKIPPED,
                    ERR_UNSUPPORTED, EXTREMA_STRIDE, FEAS_ACCEL, FEAS_BOX, FEAS_JERK, FEAS_NONFINITE, FEAS_SPEED,
                    METHOD_BAND_KKT, METHOD_DENSE_KKT, METHOD_REDUCED, NEAR_NONE, OK, SEP_CLOSE, SEP_NONFINITE, SEP_STRIDE,
-                   THRUST_HIGH, THRUST_LOW, THRUST_STRIDE, THRUST_TILT, YAW_CONSTANT, YAW_VELOCITY, Limits, TgmsError,
+                   SPLIT_AT_END, SPLIT_CHORD, SPLIT_DONE, SPLIT_FULL, SPLIT_PULL, THRUST_HIGH, THRUST_LOW, THRUST_STRIDE,
+                   THRUST_TILT, YAW_CONSTANT, YAW_VELOCITY, Limits, TgmsError,
                    ThrustLimits)
 
 __all__ = [
@@ -19,4 +20,5 @@ __all__ = [
     "SEP_STRIDE", "SEP_CLOSE", "SEP_NONFINITE", "NEAR_NONE", "CLR_BAD_OBSTACLE", "TgmsError",
     "THRUST_STRIDE", "THRUST_LOW", "THRUST_HIGH", "THRUST_TILT", "ThrustLimits",
     "COR_STRIDE", "COR_MAX_FACES", "COR_OUTSIDE", "COR_BAD_FACE",
+    "SPLIT_PULL", "SPLIT_CHORD", "SPLIT_DONE", "SPLIT_FULL", "SPLIT_AT_END",
 ]

@@ -64,7 +64,7 @@ struct tgms_handle {
     double* d_loop_ws = nullptr;
     size_t loop_ws_cap = 0;
     // tgms_neighbors_batch_device's per-vehicle boxes and knots, also tgms_clearance_batch_device's
-    // (grow-only, ordered by scratch_ev)
+    // and the per-trajectory plan of tgms_corridor_split_batch_device (grow-only, ordered by scratch_ev)
     void* d_nbr_ws = nullptr;
     size_t nbr_ws_cap = 0;
     // ragged plans: the per-M group launches fork onto these streams and join back, so
@@ -2083,6 +2083,136 @@ tgms_status tgms_corridor_batch(tgms_handle* h, int32_t B, const int32_t* so, co
     if (seg_face) std::memcpy(seg_face, p, S * sizeof(int32_t));
     if (where) std::memcpy(where, p + S * sizeof(int32_t), 2 * n * sizeof(int32_t));
     if (flags) std::memcpy(flags, p + (S + 2 * n) * sizeof(int32_t), n * sizeof(int32_t));
+    return TGMS_OK;
+}
+
+// ---- corridor split: insert waypoints at the worst excursions ----
+
+// The argument rules the two split entry points share (include/tgms.h).
+static tgms_status check_split(tgms_handle* h, int32_t B, int64_t F, const void* faces, const void* face_offsets,
+                               double r, int mode, double min_frac, const void* so_out, const void* W_out,
+                               const void* T_out, const void* faces_out, const void* fo_out, const void* totals) {
+    if (B < 0 || F < 0 || F > INT32_MAX) return set_err(h, TGMS_ERR_INVALID_ARG, "bad B or F");
+    if (!std::isfinite(r)) return set_err(h, TGMS_ERR_INVALID_ARG, "r is not finite");
+    if (mode != TGMS_SPLIT_PULL && mode != TGMS_SPLIT_CHORD) return set_err(h, TGMS_ERR_INVALID_ARG, "unknown mode");
+    if (!std::isfinite(min_frac) || !(min_frac > 0.0) || !(min_frac <= 0.5))
+        return set_err(h, TGMS_ERR_INVALID_ARG, "min_frac must be finite, > 0 and <= 0.5");
+    if (!so_out || !totals) return set_err(h, TGMS_ERR_INVALID_ARG, "seg_offsets_out or totals is NULL");
+    if (B > 0 && (!W_out || !T_out)) return set_err(h, TGMS_ERR_INVALID_ARG, "waypoints_out or seg_times_out is NULL");
+    if (F > 0 && !faces) return set_err(h, TGMS_ERR_INVALID_ARG, "faces is NULL with F > 0");
+    if (!face_offsets) {
+        if (F > TGMS_COR_MAX_FACES) return set_err(h, TGMS_ERR_INVALID_ARG, "shared faces: F > TGMS_COR_MAX_FACES");
+        if (faces_out || fo_out)
+            return set_err(h, TGMS_ERR_INVALID_ARG, "shared mode: faces_out and face_offsets_out must be NULL");
+    } else if (B > 0 && (!fo_out || (F > 0 && !faces_out))) {
+        return set_err(h, TGMS_ERR_INVALID_ARG, "faces_out or face_offsets_out is NULL");
+    }
+    return TGMS_OK;
+}
+
+// The launches of both calls, on the handle's scratch between acquire and release.
+static tgms_status split_on_device(tgms_handle* h, int32_t B, const int32_t* d_so, const double* dW, const double* dT,
+                                   const double* dC, int64_t F, const double* d_faces, const int64_t* d_fo,
+                                   const double* d_seg_rec, const int32_t* d_seg_face, double r, int mode,
+                                   double min_frac, int32_t* d_so_out, double* dW_out, double* dT_out,
+                                   double* d_faces_out, int64_t* d_fo_out, int32_t* d_parent, int64_t* d_totals,
+                                   int32_t* d_flags, hipStream_t st) {
+    tgms_status s = no_capture(h, st, "tgms_corridor_split_batch_device");
+    if (s != TGMS_OK) return s;
+    TGMS_HIP(h, hipSetDevice(h->device));
+    s = ensure_nbr_ws(h, tgms::corridor_split_scratch_bytes(B));
+    if (s == TGMS_OK) s = scratch_acquire(h, st);
+    if (s != TGMS_OK) return s;
+    return scratch_release(
+        h, st,
+        hip_err(h, tgms::launch_corridor_split(B, d_so, dW, dT, dC, F, d_faces, d_fo, d_seg_rec, d_seg_face, r, mode,
+                                               min_frac, h->d_nbr_ws, d_so_out, dW_out, dT_out, d_faces_out, d_fo_out,
+                                               d_parent, d_totals, d_flags, st),
+                "launch_corridor_split"));
+}
+
+tgms_status tgms_corridor_split_batch_device(tgms_handle* h, int32_t B, const int32_t* d_so, const double* dW,
+                                             const double* dT, const double* dC, int64_t F, const double* d_faces,
+                                             const int64_t* d_face_offsets, const double* d_seg_rec,
+                                             const int32_t* d_seg_face, double r, int mode, double min_frac,
+                                             int32_t* d_so_out, double* dW_out, double* dT_out, double* d_faces_out,
+                                             int64_t* d_fo_out, int32_t* d_parent, int64_t* d_totals,
+                                             int32_t* d_flags, void* stream) {
+    if (tgms_status e = enter(h, __func__); e != TGMS_OK) return e;
+    const tgms_status s = check_split(h, B, F, d_faces, d_face_offsets, r, mode, min_frac, d_so_out, dW_out, dT_out,
+                                      d_faces_out, d_fo_out, d_totals);
+    if (s != TGMS_OK) return s;
+    if (B > 0 && (!d_so || !dW || !dT || !dC || !d_seg_rec || !d_seg_face))
+        return set_err(h, TGMS_ERR_INVALID_ARG, "NULL device pointer");
+    TGMS_CHECK_ALIGNED(h, dW, dT, dC, d_faces, d_face_offsets, d_seg_rec, dW_out, dT_out, d_faces_out, d_fo_out,
+                       d_totals);
+    return split_on_device(h, B, d_so, dW, dT, dC, F, d_faces, d_face_offsets, d_seg_rec, d_seg_face, r, mode,
+                           min_frac, d_so_out, dW_out, dT_out, d_faces_out, d_fo_out, d_parent, d_totals, d_flags,
+                           static_cast<hipStream_t>(stream));
+}
+
+tgms_status tgms_corridor_split_batch(tgms_handle* h, int32_t B, const int32_t* so, const double* waypoints,
+                                      const double* seg_times, const double* coeffs, int64_t F, const double* faces,
+                                      const int64_t* face_offsets, const double* seg_rec, const int32_t* seg_face,
+                                      double r, int mode, double min_frac, int32_t* so_out, double* waypoints_out,
+                                      double* seg_times_out, double* faces_out, int64_t* face_offsets_out,
+                                      int32_t* parent, int64_t* totals, int32_t* flags) {
+    if (tgms_status e = enter(h); e != TGMS_OK) return e;
+    tgms_status s = check_offsets(h, B, so, TGMS_MAX_SEGMENTS, nullptr, nullptr);
+    if (s != TGMS_OK) return s;
+    s = check_split(h, B, F, faces, face_offsets, r, mode, min_frac, so_out, waypoints_out, seg_times_out, faces_out,
+                    face_offsets_out, totals);
+    if (s != TGMS_OK) return s;
+    if (B == 0) {
+        so_out[0] = 0;
+        totals[0] = 0;
+        totals[1] = face_offsets ? 0 : F;
+        return TGMS_OK;
+    }
+    if (!waypoints || !seg_times || !coeffs || !seg_rec || !seg_face) return set_err(h, TGMS_ERR_INVALID_ARG, "NULL pointer");
+    if (h->host) {
+        tgms::host::corridor_split(B, so, waypoints, seg_times, coeffs, F, faces, face_offsets, seg_rec, seg_face, r,
+                                   mode, min_frac, so_out, waypoints_out, seg_times_out, faces_out, face_offsets_out,
+                                   parent, totals, flags);
+        return TGMS_OK;
+    }
+    // one output region at the capacities of the header (2 S segments, 2 F faces), every array
+    // 16-byte aligned inside it: one download, of which the first S' / F' rows go to the caller
+    const size_t S = (size_t)so[B], n = (size_t)B, nf = face_offsets ? 2 * (size_t)F : 0;
+    auto up16 = [](size_t v) { return (v + 15) & ~size_t(15); };
+    const size_t oW = 0, oT = up16(oW + (2 * S + n) * 3 * sizeof(double)), oF = up16(oT + 2 * S * sizeof(double)),
+                 oFo = up16(oF + nf * 4 * sizeof(double)),
+                 oTot = up16(oFo + (face_offsets ? (2 * S + 1) * sizeof(int64_t) : 0)),
+                 oSo = up16(oTot + 2 * sizeof(int64_t)), oPar = up16(oSo + (n + 1) * sizeof(int32_t)),
+                 oFl = up16(oPar + 2 * S * sizeof(int32_t)), all_bytes = oFl + n * sizeof(int32_t);
+    double *dW, *dT, *dC, *dF, *dRec;
+    int64_t* dFo;
+    int32_t *dSo, *dFace;
+    char* dOut;
+    s = stage(h, {input(&dW, waypoints, (S + n) * 3), input(&dT, seg_times, S), input(&dC, coeffs, S * 24),
+                  input(&dF, faces, (size_t)F * 4), input(&dFo, face_offsets, S + 1), input(&dRec, seg_rec, S * 2),
+                  input(&dSo, so, n + 1), input(&dFace, seg_face, S), output(&dOut, all_bytes)});
+    if (s != TGMS_OK) return s;
+    s = split_on_device(h, B, dSo, dW, dT, dC, F, dF, dFo, dRec, dFace, r, mode, min_frac,
+                        reinterpret_cast<int32_t*>(dOut + oSo), reinterpret_cast<double*>(dOut + oW),
+                        reinterpret_cast<double*>(dOut + oT), nf ? reinterpret_cast<double*>(dOut + oF) : nullptr,
+                        face_offsets ? reinterpret_cast<int64_t*>(dOut + oFo) : nullptr,
+                        reinterpret_cast<int32_t*>(dOut + oPar), reinterpret_cast<int64_t*>(dOut + oTot),
+                        reinterpret_cast<int32_t*>(dOut + oFl), h->stream);
+    if (s != TGMS_OK) return s;
+    std::vector<char> all(all_bytes);
+    TGMS_HIP(h, fetch(h, all.data(), dOut, all.size()));
+    TGMS_HIP(h, hipStreamSynchronize(h->stream));
+    const char* p = all.data();
+    std::memcpy(totals, p + oTot, 2 * sizeof(int64_t));
+    const size_t S1 = (size_t)totals[0], F1 = face_offsets ? (size_t)totals[1] : 0;
+    std::memcpy(so_out, p + oSo, (n + 1) * sizeof(int32_t));
+    std::memcpy(waypoints_out, p + oW, (S1 + n) * 3 * sizeof(double));
+    std::memcpy(seg_times_out, p + oT, S1 * sizeof(double));
+    if (F1) std::memcpy(faces_out, p + oF, F1 * 4 * sizeof(double));
+    if (face_offsets) std::memcpy(face_offsets_out, p + oFo, (S1 + 1) * sizeof(int64_t));
+    if (parent) std::memcpy(parent, p + oPar, S1 * sizeof(int32_t));
+    if (flags) std::memcpy(flags, p + oFl, n * sizeof(int32_t));
     return TGMS_OK;
 }
 

@@ -28,6 +28,7 @@
 #include "tgms_bounds_core.h"
 #include "tgms_clearance_core.h"
 #include "tgms_corridor_core.h"
+#include "tgms_corridor_split_core.h"
 #include "tgms_neighbors_core.h"
 #include "tgms_separation_core.h"
 #include "tgms_thrust_core.h"
@@ -564,6 +565,78 @@ void corridor(int32_t B, const int32_t* so, const double* T, const double* C, in
             if (seg_face) seg_face[s0 + i] = face;
         }
     }
+}
+
+void corridor_split(int32_t B, const int32_t* so, const double* W, const double* T, const double* C, int64_t F,
+                    const double* faces, const int64_t* fo, const double* seg_rec, const int32_t* seg_face, double r,
+                    int mode, double min_frac, int32_t* so_out, double* W_out, double* T_out, double* faces_out,
+                    int64_t* fo_out, int32_t* parent, int64_t* totals, int32_t* flags) {
+    namespace sp = tgms::split;
+    int64_t s_out = 0, f_out = 0;  // the next segment row and face row
+    so_out[0] = 0;
+    for (int32_t b = 0; b < B; ++b) {
+        const int64_t s0 = so[b];
+        const int M = so[b + 1] - so[b];
+        const double* Tb = T + s0;
+        const double* Wb = W + (s0 + b) * 3;
+        double chk = 0.0;
+        bool bad = false;
+        for (int i = 0; i < M; ++i) {
+            chk = sp::finite_chk(Tb[i], chk);
+            bad = bad || !(Tb[i] > 0.0);
+        }
+        for (int q = 0; q < M * 24; ++q) chk = sp::finite_chk(C[s0 * 24 + q], chk);
+        for (int q = 0; q < (M + 1) * 3; ++q) chk = sp::finite_chk(Wb[q], chk);
+        bad = bad || chk != 0.0;
+        double m[TGMS_MAX_SEGMENTS], ts[TGMS_MAX_SEGMENTS];
+        int64_t fb[TGMS_MAX_SEGMENTS];
+        int cnt[TGMS_MAX_SEGMENTS];
+        for (int i = 0; i < M; ++i) {
+            m[i] = seg_rec[(s0 + i) * TGMS_COR_STRIDE];
+            ts[i] = seg_rec[(s0 + i) * TGMS_COR_STRIDE + 1];
+            fb[i] = fo ? fo[s0 + i] : 0;
+            const int64_t fe = fo ? fo[s0 + i + 1] : F;
+            cnt[i] = tgms::corridor::span_ok(fb[i], fe, F) ? (int)(fe - fb[i]) : -1;
+        }
+        const sp::Row row = sp::plan_row(M, Tb, m, ts, seg_face + s0, fb, cnt, r, bad);
+        if (flags) flags[b] = row.flags;
+        double knot = 0.0;
+        for (int i = 0; i < M; ++i) {
+            const bool cut = ((row.mask >> i) & 1) != 0;
+            const int64_t w_out = s_out + b;  // the row of this segment's start waypoint
+            std::copy(Wb + i * 3, Wb + i * 3 + 3, W_out + w_out * 3);
+            if (cut) {
+                double tl, tr, w[3];
+                sp::split_times(sp::local_time(ts[i], knot, Tb[i]), Tb[i], min_frac, tl, tr);
+                if (mode == TGMS_SPLIT_PULL) {
+                    const double* n = faces + (int64_t)seg_face[s0 + i] * 4;
+                    sp::insert_pull(C + (s0 + i) * 24, tl, n[0], n[1], n[2], n[3], r, w);
+                } else {
+                    sp::insert_chord(Wb + i * 3, Wb + i * 3 + 3, tl, Tb[i], w);
+                }
+                T_out[s_out] = tl;
+                T_out[s_out + 1] = tr;
+                std::copy(w, w + 3, W_out + (w_out + 1) * 3);
+            } else {
+                T_out[s_out] = Tb[i];
+            }
+            for (int k = 0; k < (cut ? 2 : 1); ++k) {  // each child owns a copy of the parent's span
+                if (parent) parent[s_out] = (int32_t)(s0 + i);
+                if (fo) {
+                    fo_out[s_out] = f_out;
+                    if (cnt[i] > 0) std::copy(faces + fb[i] * 4, faces + (fb[i] + cnt[i]) * 4, faces_out + f_out * 4);
+                    f_out += cnt[i] > 0 ? cnt[i] : 0;
+                }
+                ++s_out;
+            }
+            knot += Tb[i];
+        }
+        std::copy(Wb + M * 3, Wb + M * 3 + 3, W_out + (s_out + b) * 3);
+        so_out[b + 1] = (int32_t)s_out;
+    }
+    if (fo) fo_out[s_out] = f_out;
+    totals[0] = s_out;
+    totals[1] = fo ? f_out : F;
 }
 
 }  // namespace host

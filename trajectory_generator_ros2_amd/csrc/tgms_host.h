@@ -67,5 +67,14 @@ void corridor(int32_t B, const int32_t* seg_offsets, const double* seg_times, co
               const double* faces, const int64_t* face_offsets, double r, double* rec, int32_t* where,
               double* seg_rec, int32_t* seg_face, int32_t* flags);
 
+// The corridor split (include/tgms.h tgms_corridor_split_batch) of a whole batch, trajectory by
+// trajectory: the decisions of tgms_corridor_split_core.h, so every integer and every time is
+// the device's to the bit.  The offsets are valid (1..TGMS_MAX_SEGMENTS); parent and flags are
+// nullable, faces_out and fo_out unused when fo is NULL.
+void corridor_split(int32_t B, const int32_t* so, const double* W, const double* T, const double* C, int64_t F,
+                    const double* faces, const int64_t* fo, const double* seg_rec, const int32_t* seg_face, double r,
+                    int mode, double min_frac, int32_t* so_out, double* W_out, double* T_out, double* faces_out,
+                    int64_t* fo_out, int32_t* parent, int64_t* totals, int32_t* flags);
+
 }  // namespace host
 }  // namespace tgms

@@ -154,6 +154,20 @@ hipError_t launch_corridor(int32_t B, const int32_t* seg_offsets, const double* 
                            const double* faces, const int64_t* face_offsets, double r, double* rec, int32_t* where,
                            double* seg_rec, int32_t* seg_face, int32_t* flags, hipStream_t stream);
 
+// Corridor split (tgms_corridor_split.hip): the segments whose margin of a corridor call exceeds
+// -r get a waypoint at their worst excursion; the new offsets, waypoints, times, faces, face
+// offsets, parent rows (nullable), totals [2] = S' F' and flags [B] (nullable).  Five launches on
+// `stream`: the plan per tile of launch_corridor, three for the prefix sums over B, the write;
+// `scratch` holds corridor_split_scratch_bytes(B) bytes, 256-byte aligned.  face_offsets NULL:
+// shared mode, faces_out and fo_out are not touched.  B == 0 writes so_out[0] and the totals.
+size_t corridor_split_scratch_bytes(int32_t B);
+hipError_t launch_corridor_split(int32_t B, const int32_t* seg_offsets, const double* W, const double* T,
+                                 const double* C, int64_t F, const double* faces, const int64_t* face_offsets,
+                                 const double* seg_rec, const int32_t* seg_face, double r, int mode, double min_frac,
+                                 void* scratch, int32_t* so_out, double* W_out, double* T_out, double* faces_out,
+                                 int64_t* fo_out, int32_t* parent, int64_t* totals, int32_t* flags,
+                                 hipStream_t stream);
+
 // Continuous swarm separation (tgms_separation.hip): per pair the closest approach d_min t_min
 // into sep [P][TGMS_SEP_STRIDE] and flags [P] (either nullable); pairs NULL: every unordered
 // pair, decoded on the device.  A wavefront per tile of 16 pairs, one launch.

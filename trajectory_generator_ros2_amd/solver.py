@@ -213,6 +213,61 @@ class Solver:
             raise TgmsError(st, self.last_error())
         return rec, where, seg_rec, seg_face, flags
 
+    def corridor_split(self, seg_offsets, waypoints, seg_times, coeffs, faces, face_offsets, seg_rec, seg_face,
+                       r: float = 0.0, mode: int = _lib.SPLIT_PULL, min_frac: float = 0.1):
+        """Corridor split (include/tgms.h tgms_corridor_split_batch): a waypoint at the worst
+        excursion of every segment whose margin of the corridor call (seg_rec, seg_face; the same
+        faces, face_offsets and r) exceeds -r.  Returns the new batch trimmed to its S' segments and
+        F' faces: (seg_offsets' [B+1], waypoints' [S'+B,3], seg_times' [S'], faces' [F',4],
+        face_offsets' [S'+1], parent [S'], flags [B] of SPLIT_* bits); in shared mode
+        (face_offsets None) faces' is `faces` and face_offsets' is None."""
+        so = np.ascontiguousarray(seg_offsets, dtype=np.int32)
+        W = np.ascontiguousarray(waypoints, dtype=np.float64).reshape(-1, 3)
+        T = np.ascontiguousarray(seg_times, dtype=np.float64).reshape(-1)
+        C = np.ascontiguousarray(coeffs, dtype=np.float64)
+        fc = np.ascontiguousarray(faces, dtype=np.float64).reshape(-1, 4)
+        fo = None if face_offsets is None else np.ascontiguousarray(face_offsets, dtype=np.int64)
+        sr = np.ascontiguousarray(seg_rec, dtype=np.float64).reshape(-1, _lib.COR_STRIDE)
+        sf = np.ascontiguousarray(seg_face, dtype=np.int32)
+        B, S, F = so.shape[0] - 1, int(so[-1]), fc.shape[0]
+        so2 = np.zeros(B + 1, dtype=np.int32)
+        W2 = np.zeros((2 * S + B, 3), dtype=np.float64)
+        T2 = np.zeros(2 * S, dtype=np.float64)
+        fc2 = None if fo is None else np.zeros((2 * F, 4), dtype=np.float64)
+        fo2 = None if fo is None else np.zeros(2 * S + 1, dtype=np.int64)
+        parent = np.zeros(2 * S, dtype=np.int32)
+        totals = np.zeros(2, dtype=np.int64)
+        flags = np.zeros(B, dtype=np.int32)
+        st = self._L.tgms_corridor_split_batch(self._h, B, _ptr(so), _ptr(W), _ptr(T), _ptr(C), F,
+                                               _ptr(fc) if F else None, _ptr(fo), _ptr(sr), _ptr(sf), float(r),
+                                               int(mode), float(min_frac), _ptr(so2), _ptr(W2), _ptr(T2),
+                                               _ptr(fc2) if fc2 is not None and F else None, _ptr(fo2), _ptr(parent),
+                                               _ptr(totals), _ptr(flags))
+        if st != _lib.OK:
+            raise TgmsError(st, self.last_error())
+        S2, F2 = int(totals[0]), int(totals[1])
+        if fo is None:
+            return so2, W2[:S2 + B], T2[:S2], fc, None, parent[:S2], flags
+        return so2, W2[:S2 + B], T2[:S2], fc2[:F2], fo2[:S2 + 1], parent[:S2], flags
+
+    def corridor_loop(self, seg_offsets, waypoints, seg_times, faces, face_offsets, r: float, rounds: int,
+                      mode: int = _lib.SPLIT_PULL, min_frac: float = 0.1, end_derivs=None):
+        """The planner's loop on host arrays: solve, corridor, split, up to `rounds` times, stopping
+        when no trajectory carries COR_OUTSIDE.  Returns ((seg_offsets, waypoints, seg_times, faces,
+        face_offsets), coeffs, flagged): the final batch, its coefficients and the number of
+        flagged trajectories found in each round."""
+        so, W, T, fc, fo = seg_offsets, waypoints, seg_times, faces, face_offsets
+        flagged = []
+        while True:
+            C, _, worst = self.solve(so, W, T, end_derivs)
+            if worst != _lib.OK:
+                raise TgmsError(worst, self.last_error())
+            _, _, seg_rec, seg_face, fl = self.corridor(so, T, C, fc, fo, r)
+            flagged.append(int(((fl & _lib.COR_OUTSIDE) != 0).sum()))
+            if flagged[-1] == 0 or len(flagged) > rounds:
+                return (so, W, T, fc, fo), C, flagged
+            so, W, T, fc, fo, _, _ = self.corridor_split(so, W, T, C, fc, fo, seg_rec, seg_face, r, mode, min_frac)
+
     def separation(self, seg_offsets, seg_times, coeffs, pairs=None, start_times=None, scale=None,
                    r_min: float = 0.0) -> Tuple[np.ndarray, np.ndarray]:
         """Continuous swarm separation (include/tgms.h tgms_separation_batch): per pair the
@@ -414,6 +469,24 @@ class Solver:
                                                 _ptr(d_coeffs), int(F), _ptr(d_faces), _ptr(d_face_offsets),
                                                 float(r), _ptr(d_rec), _ptr(d_where), _ptr(d_seg_rec),
                                                 _ptr(d_seg_face), _ptr(d_flags), ctypes.c_void_p(stream))
+        if st != _lib.OK:
+            raise TgmsError(st, self.last_error())
+
+    def corridor_split_device(self, B: int, d_seg_offsets, d_waypoints, d_seg_times, d_coeffs, F: int, d_faces,
+                              d_face_offsets, d_seg_rec, d_seg_face, r: float, mode: int, min_frac: float,
+                              d_seg_offsets_out, d_waypoints_out, d_seg_times_out, d_faces_out=None,
+                              d_face_offsets_out=None, d_parent=None, d_totals=None, d_flags=None,
+                              stream: int = 0) -> None:
+        """tgms_corridor_split_batch_device: outputs sized for 2 S segments and 2 F faces
+        (d_seg_offsets_out [B+1] int32, d_waypoints_out [2S+B,3], d_seg_times_out [2S], d_faces_out
+        [2F,4], d_face_offsets_out [2S+1] int64, d_parent [2S] int32, d_totals [2] int64 = S' F',
+        d_flags [B] int32); shared mode (d_face_offsets None) takes no face outputs.  Not
+        capturable: it grows handle scratch with B."""
+        st = self._L.tgms_corridor_split_batch_device(
+            self._h, int(B), _ptr(d_seg_offsets), _ptr(d_waypoints), _ptr(d_seg_times), _ptr(d_coeffs), int(F),
+            _ptr(d_faces), _ptr(d_face_offsets), _ptr(d_seg_rec), _ptr(d_seg_face), float(r), int(mode),
+            float(min_frac), _ptr(d_seg_offsets_out), _ptr(d_waypoints_out), _ptr(d_seg_times_out), _ptr(d_faces_out),
+            _ptr(d_face_offsets_out), _ptr(d_parent), _ptr(d_totals), _ptr(d_flags), ctypes.c_void_p(stream))
         if st != _lib.OK:
             raise TgmsError(st, self.last_error())
 
