@@ -70,8 +70,10 @@ def test_ragged_and_loop_calls_refuse_capture(solver):
     dso, dW, dT = d(so), d(W), d(T.copy())
     S_ = int(so[-1])
     C = torch.empty((S_, 3, 8), dtype=torch.float64, device="cuda")
+    T_out = torch.empty_like(dT)
     calls = [lambda s: solver.solve_batch_device(so, dso, dW, dT, C, stream=s),
-             lambda s: solver.refine_loop_device(so, dso, dW, dT, 1.0, 0.1, 3, C, stream=s)]
+             lambda s: solver.refine_loop_device(so, dso, dW, dT, 1.0, 0.1, 3, C, stream=s),
+             lambda s: solver.refine_batch_device(so, dso, dW, dT, T_out, 1.0, 0.1, stream=s)]
     for fn in calls:
         _, err = _capture(fn)
         assert isinstance(err, TgmsError) and err.status == ERR_UNSUPPORTED, err
