@@ -43,8 +43,8 @@
  *     tgms_corridor_split_batch_device, the multi-GPU calls, a band
  *     capture with no slab large enough) return TGMS_ERR_UNSUPPORTED while their stream is
  *     capturing.
- *     tgms_extrema_batch_device, tgms_bounds_batch_device, tgms_thrust_batch_device and
- *     tgms_corridor_batch_device (one kernel, no plan, no scratch) may be captured for any
+ *     tgms_extrema_batch_device, tgms_bounds_batch_device, tgms_thrust_batch_device,
+ *     tgms_dilate_batch_device and tgms_corridor_batch_device (one kernel, no plan, no scratch) may be captured for any
  *     batch, ragged included;
  *   - there is no CPU fallback: with no usable GPU, tgms_create fails with
  *     TGMS_ERR_NO_DEVICE.  A GPU-less node asks for the host backend explicitly
@@ -116,7 +116,7 @@ tgms_status tgms_create(tgms_handle** out, int device);
 /* The explicit host backend (BASELINE config 1: a ROS 2 node with no GPU; the reference
  * generates on the executor thread's CPU, src/TrajectoryGenerator.cpp:54-57, :71).  A host
  * handle runs tgms_solve_batch (reduced method), tgms_sample_batch, tgms_extrema_batch,
- * tgms_bounds_batch, tgms_thrust_batch, tgms_corridor_batch, tgms_corridor_split_batch, tgms_separation_batch, tgms_neighbors_batch and tgms_clearance_batch on the calling thread with the GPU path's conventions; every other entry point returns
+ * tgms_bounds_batch, tgms_thrust_batch, tgms_dilate_batch, tgms_corridor_batch, tgms_corridor_split_batch, tgms_separation_batch, tgms_neighbors_batch and tgms_clearance_batch on the calling thread with the GPU path's conventions; every other entry point returns
  * TGMS_ERR_UNSUPPORTED on it.  Chosen by the caller only: tgms_create never falls back to
  * it. */
 tgms_status tgms_create_host(tgms_handle** out);
@@ -542,6 +542,93 @@ tgms_status tgms_thrust_batch_device(tgms_handle* h, int32_t B, const int32_t* d
 tgms_status tgms_thrust_batch(tgms_handle* h, int32_t B, const int32_t* seg_offsets,
                               const double* seg_times, const double* coeffs, double g,
                               const tgms_thrust_limits* limits, double* rec, int32_t* flags);
+
+/* ---- time dilation: the least uniform stretch that meets the dynamic limits ----
+ * The step after the check.  tgms_bounds_batch and tgms_thrust_batch flag a candidate; this
+ * call makes it flyable: per trajectory a dilation s in [s_lo, s_hi] such that the dilated
+ * trajectory p_s(t) = p(t / s) violates none of the given limits, and, unless s == s_lo, meets
+ * one of them, the *active* one.  The limits are v_max, a_max and j_max of `limits` (its box is
+ * ignored: position extents do not change) and f_min, f_max and tilt_max of `tlimits`; an
+ * infinite entry is unchecked, a NaN entry is TGMS_ERR_INVALID_ARG, a NULL struct is unchecked,
+ * and f_min <= 0 checks nothing.  A dilated minimum-snap optimum is the optimum of the dilated
+ * problem, so nothing is solved again: the call returns the scaled times and coefficients.
+ *   The scale interval.  0 < s_lo <= s_hi, both finite, and g finite and >= 0, else
+ * TGMS_ERR_INVALID_ARG.  s_lo < 1 speeds a slow candidate up to its tightest limit, s_lo = 1
+ * never speeds up.  A finite tilt_max must be < pi / 2 (else TGMS_ERR_INVALID_ARG): then the
+ * tilt condition is monotone in s.
+ *   How s is formed.  The peaks scale as v / s, a / s^2, j / s^3, so the kinematic part is
+ * closed form from the continuous peaks of the bounds call (not from samples),
+ *     s_kin = max(v_peak / v_max, sqrt(a_peak / a_max), cbrt(j_peak / j_max)).
+ * Gravity does not scale with time: f_s = p''(t / s) / s^2 + g e_z.  With lambda = 1 / s^2 this
+ * is lambda (p'' + (g / lambda) e_z), so the thrust record of the dilated trajectory is the
+ * record of the thrust call on the undilated coefficients at g' = g / lambda, the norms times
+ * lambda, the tilt unchanged.  The thrust part is a bracketed root search in lambda over (0,
+ * 1 / max(s_lo, s_kin)^2] on that record (Illinois steps with bisection as the safeguard, at
+ * most 163 evaluations, about 10 on typical input).  f_max is convex and the tilt condition linear in
+ * lambda, so each is crossed once.  f_min can be crossed several times when a trajectory
+ * passes near free fall: then some crossing from feasible to infeasible is returned; the
+ * returned s is still feasible, and minimal only locally.  The result is the FEASIBLE end of
+ * the final bracket, whose relative width in lambda is 2^-41.  A trajectory that is feasible at
+ * max(s_lo, s_kin) costs one evaluation.
+ *   scale[b] = s.  active[b] is a TGMS_DIL_* code: TGMS_DIL_NONE when s == s_lo, else the limit
+ * met.  flags[b]: TGMS_DIL_CAPPED when the trajectory is still infeasible at s_hi (limits that
+ * exclude hover, f_max <= g and the like, end here): then s = s_hi, the outputs are scaled by
+ * s_hi, and active is the limit that is worst there, by the largest of the relative excesses
+ * v / v_max - 1, a / a_max - 1, j / j_max - 1, f_max / limit - 1, 1 - f_min / limit and the
+ * tilt's excess in radians.  Bits TGMS_DIL_EVALS_SHIFT.. of flags hold the number of
+ * evaluations of the thrust record the trajectory took (a diagnostic of the cost, at most 163;
+ * host and device may differ in it): (flags >> TGMS_DIL_EVALS_SHIFT); the low bits are
+ * flags & TGMS_DIL_FLAG_MASK.
+ *   Outputs.  seg_times_out[i] = s T_i, and coefficient k of every segment and axis becomes
+ * c_k r^k with r = 1 / s, the power formed by repeated multiplication (r, r r, (r r) r, ...):
+ * that rule is part of the interface, so host and device write the same bits for the same s.
+ * Each output pointer may be exactly the corresponding input pointer (in place) or an array
+ * that does not overlap it; partial overlap is undefined.  In place and out of place give the
+ * same bits.  Coefficients solved with non-zero end derivatives come out with those derivatives
+ * scaled too (v / s, a / s^2, j / s^3 at both ends): a caller whose start state is fixed and
+ * moving must solve again with the scaled times instead.
+ *   An unusable trajectory (a non-finite coefficient or time, T_i <= 0, a non-finite result or,
+ * in the device call, a segment count outside 1..TGMS_MAX_SEGMENTS) gets s = NaN, active = -1
+ * and TGMS_FEAS_NONFINITE alone; its output rows are copied unchanged, and for a bad segment
+ * count nothing is read or written for its segments.  Its neighbours are unaffected: no
+ * result depends on the other trajectories of the batch.
+ *   Accuracy, free of conditioning: let the bounds and thrust records of the OUTPUT be taken.
+ * Feasible: no peak exceeds its limit by more than 1e-9 relative; f_min >= limit (1 - 1e-9 F /
+ * limit); the tilt exceeds its limit by no more than 1e-9 F / f_min rad, F the thrust record's
+ * f_max.  Tight: where active != TGMS_DIL_NONE and the trajectory is not capped, the active
+ * quantity is within 1e-9 relative of its limit (the tilt within the absolute bound above).
+ *   At least one output must be non-NULL; fp64 device arrays are 16-byte aligned; B == 0 is
+ * TGMS_OK and launches nothing.  tgms_dilate_batch_device is one kernel launch with no host plan
+ * and no handle scratch, so it may be captured into a HIP graph for any batch.  On a multi
+ * handle it runs on device 0; on a host handle it returns TGMS_ERR_UNSUPPORTED.
+ * tgms_dilate_batch on a host handle computes on the calling thread (the same algorithm; host
+ * and device agree to the accuracy above, not to the bit); on a GPU handle it does one upload,
+ * the launch and one download. */
+#define TGMS_DIL_CAPPED 1 /* still infeasible at s_hi: outputs are scaled by s_hi */
+/* TGMS_FEAS_NONFINITE (16) is reused */
+#define TGMS_DIL_FLAG_MASK 0xff
+#define TGMS_DIL_EVALS_SHIFT 8 /* flags >> 8: evaluations of the thrust record */
+enum {
+    TGMS_DIL_NONE = 0, /* s == s_lo, no limit is active */
+    TGMS_DIL_SPEED,
+    TGMS_DIL_ACCEL,
+    TGMS_DIL_JERK,
+    TGMS_DIL_THRUST_HIGH,
+    TGMS_DIL_THRUST_LOW,
+    TGMS_DIL_TILT
+};
+tgms_status tgms_dilate_batch_device(tgms_handle* h, int32_t B, const int32_t* d_seg_offsets,
+                                     const double* d_seg_times, const double* d_coeffs, double g,
+                                     const tgms_limits* limits /* host, nullable; pmin/pmax ignored */,
+                                     const tgms_thrust_limits* tlimits /* host, nullable */, double s_lo,
+                                     double s_hi, double* d_scale /* [B], nullable */,
+                                     int32_t* d_active /* [B], nullable */, int32_t* d_flags /* [B], nullable */,
+                                     double* d_seg_times_out /* [S], nullable */,
+                                     double* d_coeffs_out /* [S][3][8], nullable */, void* stream);
+tgms_status tgms_dilate_batch(tgms_handle* h, int32_t B, const int32_t* seg_offsets, const double* seg_times,
+                              const double* coeffs, double g, const tgms_limits* limits,
+                              const tgms_thrust_limits* tlimits, double s_lo, double s_hi, double* scale,
+                              int32_t* active, int32_t* flags, double* seg_times_out, double* coeffs_out);
 
 /* ---- corridor containment: worst excursion from per-segment convex polytopes ----
  * Does each segment stay inside its safe flight corridor.  Waypoints come from a path through

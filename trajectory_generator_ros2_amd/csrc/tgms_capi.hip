@@ -13,6 +13,7 @@
 #include "tgms_internal.h"
 #include "tgms_plan.h"
 #include "tgms_host.h"
+#include "tgms_dilate_core.h"
 #include "tgms_separation_core.h"
 
 #include <dlfcn.h>
@@ -2009,6 +2010,110 @@ tgms_status tgms_thrust_batch(tgms_handle* h, int32_t B, const int32_t* so, cons
     if (s != TGMS_OK) return s;
     TGMS_HIP(h, tgms::launch_thrust(B, dSo, dT, dC, g, lim, res.d_rec(), res.d_flags(), h->stream));
     return download(h, res);
+}
+
+// ---- time dilation: the least uniform stretch that meets the dynamic limits ----
+
+// The argument rules the two dilation entry points share (include/tgms.h), and the six limits a
+// launch carries: +inf is unchecked (f_lo: <= 0), an infinite entry of either sign or a NULL
+// struct likewise.
+static tgms_status check_dilate(tgms_handle* h, int32_t B, double g, const tgms_limits* limits,
+                                const tgms_thrust_limits* tlimits, double s_lo, double s_hi, bool any_output,
+                                tgms::dilate::Lim* out) {
+    const double inf = std::numeric_limits<double>::infinity();
+    if (B < 0 || !(g >= 0.0) || !std::isfinite(g)) return set_err(h, TGMS_ERR_INVALID_ARG, "bad B or g");
+    if (!(s_lo > 0.0) || !(s_lo <= s_hi) || !std::isfinite(s_hi))
+        return set_err(h, TGMS_ERR_INVALID_ARG, "the scale interval needs 0 < s_lo <= s_hi, both finite");
+    *out = tgms::dilate::Lim{inf, inf, inf, 0.0, inf, inf};
+    if (limits) {
+        if (std::isnan(limits->v_max) || std::isnan(limits->a_max) || std::isnan(limits->j_max))
+            return set_err(h, TGMS_ERR_INVALID_ARG, "NaN limit");
+        if (std::isfinite(limits->v_max)) out->v_max = limits->v_max;
+        if (std::isfinite(limits->a_max)) out->a_max = limits->a_max;
+        if (std::isfinite(limits->j_max)) out->j_max = limits->j_max;
+    }
+    tgms_thrust_limits tl;
+    if (!resolve_thrust_limits(tlimits, &tl)) return set_err(h, TGMS_ERR_INVALID_ARG, "NaN limit");
+    if (std::isfinite(tl.tilt_max) && !(tl.tilt_max < 1.5707963267948966))
+        return set_err(h, TGMS_ERR_INVALID_ARG, "a finite tilt_max must be < pi / 2");
+    out->f_lo = std::isfinite(tl.f_min) ? tl.f_min : 0.0;
+    out->f_hi = tl.f_max;
+    out->tilt = tl.tilt_max;
+    if (!any_output) return set_err(h, TGMS_ERR_INVALID_ARG, "every output is NULL");
+    return TGMS_OK;
+}
+
+tgms_status tgms_dilate_batch_device(tgms_handle* h, int32_t B, const int32_t* d_so, const double* dT,
+                                     const double* dC, double g, const tgms_limits* limits,
+                                     const tgms_thrust_limits* tlimits, double s_lo, double s_hi, double* d_scale,
+                                     int32_t* d_active, int32_t* d_flags, double* dT_out, double* dC_out,
+                                     void* stream) {
+    if (tgms_status e = enter(h, __func__); e != TGMS_OK) return e;
+    tgms::dilate::Lim lim;
+    const tgms_status s = check_dilate(h, B, g, limits, tlimits, s_lo, s_hi,
+                                       d_scale || d_active || d_flags || dT_out || dC_out, &lim);
+    if (s != TGMS_OK) return s;
+    if (B == 0) return TGMS_OK;
+    if (!d_so || !dT || !dC) return set_err(h, TGMS_ERR_INVALID_ARG, "NULL device pointer");
+    TGMS_CHECK_ALIGNED(h, dT, dC, d_scale, dT_out, dC_out);
+    TGMS_HIP(h, tgms::launch_dilate(B, d_so, dT, dC, g, lim, s_lo, s_hi, d_scale, d_active, d_flags, dT_out, dC_out,
+                                    static_cast<hipStream_t>(stream)));
+    return TGMS_OK;
+}
+
+tgms_status tgms_dilate_batch(tgms_handle* h, int32_t B, const int32_t* so, const double* seg_times,
+                              const double* coeffs, double g, const tgms_limits* limits,
+                              const tgms_thrust_limits* tlimits, double s_lo, double s_hi, double* scale,
+                              int32_t* active, int32_t* flags, double* seg_times_out, double* coeffs_out) {
+    if (tgms_status e = enter(h); e != TGMS_OK) return e;
+    tgms_status s = check_offsets(h, B, so, TGMS_MAX_SEGMENTS, nullptr, nullptr);
+    if (s != TGMS_OK) return s;
+    tgms::dilate::Lim lim;
+    s = check_dilate(h, B, g, limits, tlimits, s_lo, s_hi, scale || active || flags || seg_times_out || coeffs_out,
+                     &lim);
+    if (s != TGMS_OK) return s;
+    if (B == 0) return TGMS_OK;
+    if (!seg_times || !coeffs) return set_err(h, TGMS_ERR_INVALID_ARG, "NULL pointer");
+    if (h->host) {
+        for (int32_t b = 0; b < B; ++b) {
+            const int64_t s0 = so[b];
+            double sc;
+            int act;
+            const int fl = tgms::host::dilate(so[b + 1] - so[b], coeffs + s0 * 24, seg_times + s0, g, lim, s_lo, s_hi,
+                                              &sc, &act, seg_times_out ? seg_times_out + s0 : nullptr,
+                                              coeffs_out ? coeffs_out + s0 * 24 : nullptr);
+            if (scale) scale[b] = sc;
+            if (active) active[b] = act;
+            if (flags) flags[b] = fl;
+        }
+        return TGMS_OK;
+    }
+    // one output region, every array 16-byte aligned inside it: one download, split on the host
+    const size_t S = (size_t)so[B], n = (size_t)B;
+    auto up16 = [](size_t v) { return (v + 15) & ~size_t(15); };
+    const size_t oC = 0, oT = up16(oC + (coeffs_out ? S * 24 * sizeof(double) : 0)),
+                 oS = up16(oT + (seg_times_out ? S * sizeof(double) : 0)), oA = up16(oS + (scale ? n * sizeof(double) : 0)),
+                 oF = up16(oA + (active ? n * sizeof(int32_t) : 0)), all_bytes = oF + (flags ? n * sizeof(int32_t) : 0);
+    double *dT, *dC;
+    int32_t* dSo;
+    char* dOut;
+    s = stage(h, {input(&dT, seg_times, S), input(&dC, coeffs, S * 24), input(&dSo, so, n + 1), output(&dOut, all_bytes)});
+    if (s != TGMS_OK) return s;
+    TGMS_HIP(h, tgms::launch_dilate(B, dSo, dT, dC, g, lim, s_lo, s_hi, scale ? reinterpret_cast<double*>(dOut + oS) : nullptr,
+                                    active ? reinterpret_cast<int32_t*>(dOut + oA) : nullptr,
+                                    flags ? reinterpret_cast<int32_t*>(dOut + oF) : nullptr,
+                                    seg_times_out ? reinterpret_cast<double*>(dOut + oT) : nullptr,
+                                    coeffs_out ? reinterpret_cast<double*>(dOut + oC) : nullptr, h->stream));
+    std::vector<char> all(all_bytes);
+    TGMS_HIP(h, fetch(h, all.data(), dOut, all.size()));
+    TGMS_HIP(h, hipStreamSynchronize(h->stream));
+    const char* p = all.data();
+    if (coeffs_out) std::memcpy(coeffs_out, p + oC, S * 24 * sizeof(double));
+    if (seg_times_out) std::memcpy(seg_times_out, p + oT, S * sizeof(double));
+    if (scale) std::memcpy(scale, p + oS, n * sizeof(double));
+    if (active) std::memcpy(active, p + oA, n * sizeof(int32_t));
+    if (flags) std::memcpy(flags, p + oF, n * sizeof(int32_t));
+    return TGMS_OK;
 }
 
 // ---- corridor containment: worst excursion from per-segment polytopes ----

@@ -29,6 +29,7 @@
 #include "tgms_clearance_core.h"
 #include "tgms_corridor_core.h"
 #include "tgms_corridor_split_core.h"
+#include "tgms_dilate_core.h"
 #include "tgms_neighbors_core.h"
 #include "tgms_separation_core.h"
 #include "tgms_thrust_core.h"
@@ -364,6 +365,51 @@ int thrust(int M, const double* C, const double* T, double g, const tgms_thrust_
     const int fl = th::finish(f, bad, lim ? *lim : none, r);
     for (int q = 0; q < TGMS_THRUST_STRIDE; ++q) rec[q] = r[q];
     return fl;
+}
+
+int dilate(int M, const double* C, const double* T, double g, const tgms::dilate::Lim& lim, double s_lo, double s_hi,
+           double* scale, int* active, double* T_out, double* C_out) {
+    namespace th = tgms::thrust;
+    namespace dl = tgms::dilate;
+    double chk = 0.0;
+    const bool badM = M < 1 || M > TGMS_MAX_SEGMENTS;
+    bool bad = badM;
+    for (int i = 0; !bad && i < M; ++i) {
+        chk += T[i] * 0.0;
+        bad = bad || !(T[i] > 0.0);
+    }
+    for (int q = 0; !bad && q < M * 24; ++q) chk += C[q] * 0.0;
+    bad = bad || !finite(chk);
+    const double inf = HUGE_VAL;
+    double n2[3] = {0.0, 0.0, 0.0};
+    for (int i = 0; !bad && i < M; ++i) {  // phase 1 of the kernel: the peaks, unchecked ones skipped
+        const double r[3] = {lim.v_max < inf ? tgms::bounds::norm_item<1>(C + i * 24, T[i]) : 0.0,
+                             tgms::bounds::norm_item<2>(C + i * 24, T[i]),
+                             lim.j_max < inf ? tgms::bounds::norm_item<3>(C + i * 24, T[i]) : 0.0};
+        for (int a = 0; a < 3; ++a) n2[a] = std::fmax(n2[a], r[a] == r[a] ? r[a] : inf);
+    }
+    dl::Search q;
+    dl::init(q, bad, dl::Kin{std::sqrt(n2[0]), std::sqrt(n2[1]), std::sqrt(n2[2])}, g, lim, s_lo, s_hi);
+    for (int round = 0; q.stage != dl::ST_DONE && round < dl::MAX_EVALS + 3; ++round) {  // phase 2: the search
+        const double gp = g / q.x;
+        th::Fold f = th::fold_init();
+        for (int i = 0; i < M; ++i) {
+            th::Item it;
+            th::thrust_item(C + i * 24, T[i], gp, it);
+            if (lim.tilt < inf) th::tilt_item(C + i * 24, T[i], gp, it);
+            th::fold(f, it, T[i]);
+        }
+        dl::step(q, f, lim, s_lo, s_hi);
+    }
+    const bool keep = !(q.s == q.s);  // unusable: the rows are copied unchanged
+    const double r = keep ? 1.0 : 1.0 / q.s;
+    if (!badM) {  // phase 3; the inputs may be the outputs, each element is read before it is written
+        for (int e = 0; C_out && e < M * 24; ++e) C_out[e] = keep ? C[e] : dl::scaled(C[e], e & 7, r);
+        for (int i = 0; T_out && i < M; ++i) T_out[i] = keep ? T[i] : q.s * T[i];
+    }
+    if (scale) *scale = q.s;
+    if (active) *active = q.active;
+    return q.flags;
 }
 
 int separation(int Mi, const double* ci, const double* Ti, double t0i, int Mj, const double* cj, const double* Tj,

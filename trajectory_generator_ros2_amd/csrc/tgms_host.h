@@ -7,6 +7,9 @@
 #include "tgms.h"
 
 namespace tgms {
+namespace dilate {
+struct Lim;
+}
 namespace host {
 
 // One trajectory (include/tgms.h layouts): waypoints [M+1][3], seg_times [M], end_derivs
@@ -36,6 +39,14 @@ int bounds(int M, const double* coeffs, const double* seg_times, const tgms_limi
 // (tgms_thrust_core.h), one segment after the other.
 int thrust(int M, const double* coeffs, const double* seg_times, double g, const tgms_thrust_limits* lim,
            double* rec);
+
+// Time dilation (include/tgms.h tgms_dilate_batch) of one trajectory: the least stretch in
+// [s_lo, s_hi] that meets lim (tgms_dilate_core.h, resolved) into *scale, the TGMS_DIL_* code of
+// the active limit into *active, the scaled times into T_out [M] and coefficients into C_out
+// [M][3][8] (each nullable; T_out / C_out may be seg_times / coeffs); returns the flags.  The
+// algorithm is the kernel's (tgms_dilate_core.h), one segment and one evaluation after the other.
+int dilate(int M, const double* coeffs, const double* seg_times, double g, const tgms::dilate::Lim& lim, double s_lo,
+           double s_hi, double* scale, int* active, double* T_out, double* C_out);
 
 // Closest approach of one pair (include/tgms.h tgms_separation_batch): trajectory i has Mi
 // segments (coeffs ci, times Ti) and starts at t0i, likewise j.  Mi or Mj == 0 says that the

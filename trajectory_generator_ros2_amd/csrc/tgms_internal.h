@@ -145,6 +145,17 @@ hipError_t launch_bounds(int32_t B, const int32_t* seg_offsets, const double* T,
 hipError_t launch_thrust(int32_t B, const int32_t* seg_offsets, const double* T, const double* C, double g,
                          const tgms_thrust_limits& lim, double* rec, int32_t* flags, hipStream_t stream);
 
+// Time dilation (tgms_dilate.hip): per trajectory the least stretch s in [s_lo, s_hi] that meets
+// lim (tgms_dilate_core.h: the six limits, resolved) into scale [B], the active limit into active
+// [B], flags [B], the scaled times into T_out [S] and coefficients into C_out [S][3][8] (each
+// nullable; T_out / C_out may be T / C); the mapping of launch_thrust, one launch.
+namespace dilate {
+struct Lim;
+}
+hipError_t launch_dilate(int32_t B, const int32_t* seg_offsets, const double* T, const double* C, double g,
+                         const dilate::Lim& lim, double s_lo, double s_hi, double* scale, int32_t* active,
+                         int32_t* flags, double* T_out, double* C_out, hipStream_t stream);
+
 // Corridor containment (tgms_corridor.hip): per trajectory m_max t_max into rec
 // [B][TGMS_COR_STRIDE], its segment and face into where [B][2], per segment m_s t_s into
 // seg_rec [S][TGMS_COR_STRIDE] and its face into seg_face [S], flags [B] (each nullable);

@@ -189,6 +189,29 @@ class Solver:
             raise TgmsError(st, self.last_error())
         return rec, flags
 
+    def dilate(self, seg_offsets, seg_times, coeffs, g: float = 9.80665, limits: Optional[_lib.Limits] = None,
+               tlimits: Optional[_lib.ThrustLimits] = None, s_lo: float = 1.0, s_hi: float = 100.0):
+        """Time dilation (include/tgms.h tgms_dilate_batch): per trajectory the least stretch s in
+        [s_lo, s_hi] that meets v_max / a_max / j_max of `limits` and f_min / f_max / tilt_max of
+        `tlimits` (None: unchecked).  Returns (scale [B], active [B] of DIL_* codes, flags [B] =
+        DIL_CAPPED / FEAS_NONFINITE with the evaluation count above DIL_EVALS_SHIFT, seg_times_out
+        [S] = s T, coeffs_out [S,3,8] = c_k / s^k)."""
+        so = np.ascontiguousarray(seg_offsets, dtype=np.int32)
+        T = np.ascontiguousarray(seg_times, dtype=np.float64).reshape(-1)
+        C = np.ascontiguousarray(coeffs, dtype=np.float64)
+        B = so.shape[0] - 1
+        scale = np.zeros(B, dtype=np.float64)
+        active = np.zeros(B, dtype=np.int32)
+        flags = np.zeros(B, dtype=np.int32)
+        T_out, C_out = np.zeros_like(T), np.zeros_like(C)
+        st = self._L.tgms_dilate_batch(self._h, B, _ptr(so), _ptr(T), _ptr(C), float(g),
+                                       None if limits is None else ctypes.byref(limits),
+                                       None if tlimits is None else ctypes.byref(tlimits), float(s_lo), float(s_hi),
+                                       _ptr(scale), _ptr(active), _ptr(flags), _ptr(T_out), _ptr(C_out))
+        if st != _lib.OK:
+            raise TgmsError(st, self.last_error())
+        return scale, active, flags, T_out, C_out
+
     def corridor(self, seg_offsets, seg_times, coeffs, faces, face_offsets=None, r: float = 0.0):
         """Corridor containment (include/tgms.h tgms_corridor_batch): faces [F,4] = n[3] d, a point
         inside when n . p <= d; face_offsets [S+1] int64 gives each segment its faces, None
@@ -456,6 +479,22 @@ class Solver:
                                               _ptr(d_coeffs), float(g),
                                               None if limits is None else ctypes.byref(limits),
                                               _ptr(d_rec), _ptr(d_flags), ctypes.c_void_p(stream))
+        if st != _lib.OK:
+            raise TgmsError(st, self.last_error())
+
+    def dilate_device(self, B: int, d_seg_offsets, d_seg_times, d_coeffs, g: float = 9.80665,
+                      limits: Optional[_lib.Limits] = None, tlimits: Optional[_lib.ThrustLimits] = None,
+                      s_lo: float = 1.0, s_hi: float = 100.0, d_scale=None, d_active=None, d_flags=None,
+                      d_seg_times_out=None, d_coeffs_out=None, stream: int = 0) -> None:
+        """tgms_dilate_batch_device: d_scale [B] fp64, d_active [B] int32, d_flags [B] int32,
+        d_seg_times_out [S] fp64, d_coeffs_out [S,3,8] fp64 (at least one; the last two may be the
+        inputs themselves); g and the limits are read now, so they may change before the kernel runs."""
+        st = self._L.tgms_dilate_batch_device(self._h, int(B), _ptr(d_seg_offsets), _ptr(d_seg_times),
+                                              _ptr(d_coeffs), float(g),
+                                              None if limits is None else ctypes.byref(limits),
+                                              None if tlimits is None else ctypes.byref(tlimits), float(s_lo),
+                                              float(s_hi), _ptr(d_scale), _ptr(d_active), _ptr(d_flags),
+                                              _ptr(d_seg_times_out), _ptr(d_coeffs_out), ctypes.c_void_p(stream))
         if st != _lib.OK:
             raise TgmsError(st, self.last_error())
 
