@@ -40,7 +40,7 @@
  *     handle must be replayed in stream order with each other.  Calls that upload a
  *     host-side launch plan or grow scratch at call time (ragged batches,
  *     tgms_refine_loop_device, tgms_neighbors_batch_device, tgms_clearance_batch_device,
- *     tgms_corridor_split_batch_device, the multi-GPU calls, a band
+ *     tgms_corridor_split_batch_device, tgms_cut_batch_device, the multi-GPU calls, a band
  *     capture with no slab large enough) return TGMS_ERR_UNSUPPORTED while their stream is
  *     capturing.
  *     tgms_extrema_batch_device, tgms_bounds_batch_device, tgms_thrust_batch_device,
@@ -116,7 +116,7 @@ tgms_status tgms_create(tgms_handle** out, int device);
 /* The explicit host backend (BASELINE config 1: a ROS 2 node with no GPU; the reference
  * generates on the executor thread's CPU, src/TrajectoryGenerator.cpp:54-57, :71).  A host
  * handle runs tgms_solve_batch (reduced method), tgms_sample_batch, tgms_extrema_batch,
- * tgms_bounds_batch, tgms_thrust_batch, tgms_dilate_batch, tgms_corridor_batch, tgms_corridor_split_batch, tgms_separation_batch, tgms_neighbors_batch and tgms_clearance_batch on the calling thread with the GPU path's conventions; every other entry point returns
+ * tgms_bounds_batch, tgms_thrust_batch, tgms_dilate_batch, tgms_corridor_batch, tgms_corridor_split_batch, tgms_cut_batch, tgms_separation_batch, tgms_neighbors_batch and tgms_clearance_batch on the calling thread with the GPU path's conventions; every other entry point returns
  * TGMS_ERR_UNSUPPORTED on it.  Chosen by the caller only: tgms_create never falls back to
  * it. */
 tgms_status tgms_create_host(tgms_handle** out);
@@ -797,6 +797,89 @@ tgms_status tgms_corridor_split_batch(tgms_handle* h, int32_t B, const int32_t* 
                                       double min_frac, int32_t* seg_offsets_out, double* waypoints_out,
                                       double* seg_times_out, double* faces_out, int64_t* face_offsets_out,
                                       int32_t* parent, int64_t* totals, int32_t* flags);
+
+/* ---- replan cut: restart each trajectory from its state at a given time ----
+ * What a planner does on every tick after the first: vehicle b is at time t_cut[b] of its solved
+ * trajectory and is replanned from where it is.  The call rebuilds the batch -- seg_offsets,
+ * waypoints, seg_times and end_derivs -- without the segments that lie behind, with the segment
+ * the vehicle is in shortened and with its state (p, v, a, j) there as the start, ready for the
+ * next tgms_solve_batch_device.  A minimum-snap trajectory is the optimum of a problem whose
+ * state is (p, p', p'', p''') and whose control is the snap, so the tail of an optimum is the
+ * optimum of the tail problem: solving the output reproduces the old tail (d_coeffs_out) unless
+ * the caller moves a waypoint first.  No output can be larger than its input: d_seg_offsets_out
+ * [B+1], d_waypoints_out [S+B][3], d_seg_times_out [S], d_end_derivs_out [B][2][3][3],
+ * d_coeffs_out [S][3][8], d_parent [S], d_t0_out [B], d_flags [B], S = seg_offsets[B];
+ * d_totals [1] receives S', the segment rows that were written.
+ *   Knots.  k_0 = 0, k_m+1 = k_m + T_m, added left to right, each sum rounded: the corridor
+ * call's prefix sum.  D = k_M.
+ *   Where the cut falls.  t_cut[b] >= D finishes the trajectory (below).  Otherwise t_c =
+ * min(max(t_cut[b], 0), D); s is the number of m in 1..M-1 with k_m <= t_c, so a cut exactly on an
+ * interior knot belongs to the later segment at local time 0; t_loc = min(max(t_c - k_s, 0), T_s)
+ * and rem = T_s - t_loc.  If rem <= 0 or rem < min_frac T_s (product and comparison in plain
+ * fp64, no fused multiply-add) the cut snaps forward to knot s+1: off the last segment the
+ * trajectory is finished, else s <- s+1, t_loc = 0 and TGMS_CUT_SNAPPED is set.  min_frac is
+ * finite with 0 <= min_frac < 1, else TGMS_ERR_INVALID_ARG; it exists because a vanishing first
+ * segment ruins the conditioning of the solve that follows.
+ *   The rows of a usable, unfinished trajectory.  M' = M - s.  Times: T_s - t_loc (one rounded
+ * subtraction) when t_loc > 0, else T_s copied; then T_s+1 .. copied bit for bit.  Waypoints: the
+ * first is w_s copied bit for bit when t_loc == 0, else p(t_loc) from the three axis Horner
+ * chains of segment s; then w_s+1 .. w_M copied.  Start of end_derivs_out: when s == 0 and
+ * t_loc == 0 the input's start derivatives (zeros when d_end_derivs is NULL), else p', p'', p'''
+ * of segment s at t_loc; its final half is the input's, or zeros.  coeffs_out: segment s
+ * Taylor-shifted to local time 0 at t_loc (copied when t_loc == 0), the rest copied bit for bit:
+ * the tail without a solve.  parent[s'] is the input segment row that s' came from, so a caller
+ * can carry face spans or other per-segment data.  t0_out = k_s + t_loc (one add) is the time on
+ * the old clock at which the new trajectory starts: what a caller adds to start_times for the
+ * separation call.  TGMS_CUT_DONE says that something was removed (s > 0 or t_loc > 0); a cut at
+ * or before 0, -inf included, reproduces the trajectory bit for bit with no flag.
+ *   Finished (TGMS_CUT_FINISHED with TGMS_CUT_DONE, never TGMS_CUT_SNAPPED: the cut is at or
+ * beyond D, +inf included, or snapped off the last segment).  One hold segment, the separation
+ * call's convention (the vehicle holds the end point): waypoints (w_M, w_M), the time T_M-1
+ * copied, all six end derivatives zero, coeffs_out the constant w_M, parent the last input row,
+ * t0_out = D.
+ *   Unusable trajectories.  A trajectory with a non-finite coefficient, time, waypoint or end
+ * derivative, a NaN t_cut, or a time that is not > 0 is copied through unchanged with
+ * TGMS_FEAS_NONFINITE alone; its t0_out is NaN and its end_derivs_out the input row or zeros.
+ * In the device call a segment count outside 1..TGMS_MAX_SEGMENTS means that nothing can be read
+ * for the trajectory: it becomes the split's placeholder -- one segment with a NaN time, two NaN
+ * waypoints, NaN end derivatives and coefficients, parent TGMS_NEAR_NONE, t0_out NaN -- so that
+ * the output stays a valid CSR and the solve that follows reports TGMS_ERR_INVALID_ARG for that
+ * row alone; its neighbours are unaffected.  Only such offsets can make the output exceed the
+ * capacities above; rows beyond them are then not written, so no write lands outside a buffer.
+ *   Accuracy.  A state value of order k is within 1e-9 sum_j j!/(j-k)! |c_j| t_loc^(j-k) of the
+ * exact derivative of segment s, a shifted coefficient k within 1e-9 sum_j C(j,k) |c_j|
+ * t_loc^(j-k): Horner condition sums.  The host backend's integers, flags, times and t0_out are
+ * the device's to the bit; states and shifted coefficients agree to that accuracy.
+ *   No result depends on the launch shape, and a repeated call gives the same bits.  Outputs must
+ * not overlap inputs (the compaction moves rows across workgroups).  d_seg_offsets_out,
+ * d_waypoints_out, d_seg_times_out, d_end_derivs_out and d_totals are required, the other outputs
+ * nullable; d_end_derivs NULL is rest to rest.  The fp64 arrays are 16-byte aligned.  B == 0 is
+ * TGMS_OK, writes d_seg_offsets_out[0] = 0 and d_totals = 0 and nothing else.  The device call
+ * runs five launches on `stream` (plan, the split's three for the prefix sum, write) on handle
+ * scratch that grows with B: like tgms_corridor_split_batch_device it returns
+ * TGMS_ERR_UNSUPPORTED while its stream is capturing and is ordered among the handle's other
+ * scratch users.  On a multi handle it runs on device 0; on a host handle it returns
+ * TGMS_ERR_UNSUPPORTED.  tgms_cut_batch on a host handle computes on the calling thread; on a GPU
+ * handle it does one upload, the launches and one download, and copies the first S' rows to the
+ * caller. */
+#define TGMS_CUT_DONE 1     /* something was removed: s > 0 or t_loc > 0 */
+#define TGMS_CUT_SNAPPED 2  /* too little of segment s was left: the cut moved forward to knot s+1 */
+#define TGMS_CUT_FINISHED 4 /* nothing is left: one hold segment at the last waypoint */
+/* TGMS_FEAS_NONFINITE (16) and TGMS_NEAR_NONE (-1) are reused */
+tgms_status tgms_cut_batch_device(tgms_handle* h, int32_t B, const int32_t* d_seg_offsets,
+                                  const double* d_waypoints, const double* d_seg_times,
+                                  const double* d_end_derivs /* nullable */, const double* d_coeffs,
+                                  const double* d_t_cut /* [B] */, double min_frac,
+                                  int32_t* d_seg_offsets_out /* [B+1] */, double* d_waypoints_out /* [S+B][3] */,
+                                  double* d_seg_times_out /* [S] */, double* d_end_derivs_out /* [B][2][3][3] */,
+                                  double* d_coeffs_out /* [S][3][8], nullable */, int32_t* d_parent /* [S], nullable */,
+                                  double* d_t0_out /* [B], nullable */, int64_t* d_totals /* [1]: S' */,
+                                  int32_t* d_flags /* [B], nullable */, void* stream);
+tgms_status tgms_cut_batch(tgms_handle* h, int32_t B, const int32_t* seg_offsets, const double* waypoints,
+                           const double* seg_times, const double* end_derivs, const double* coeffs,
+                           const double* t_cut, double min_frac, int32_t* seg_offsets_out, double* waypoints_out,
+                           double* seg_times_out, double* end_derivs_out, double* coeffs_out, int32_t* parent,
+                           double* t0_out, int64_t* totals, int32_t* flags);
 
 /* ---- multi-GPU ----
  * One process drives devices 0 .. device_count-1 through one handle that owns one RCCL

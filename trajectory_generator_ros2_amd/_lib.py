@@ -34,6 +34,7 @@ COR_MAX_FACES = 256  # faces of one segment at most
 COR_OUTSIDE, COR_BAD_FACE = 1, 32  # with FEAS_NONFINITE; indices use NEAR_NONE
 SPLIT_PULL, SPLIT_CHORD = 0, 1  # the inserted waypoint of tgms_corridor_split_batch
 SPLIT_DONE, SPLIT_FULL, SPLIT_AT_END = 1, 2, 4  # with FEAS_NONFINITE
+CUT_DONE, CUT_SNAPPED, CUT_FINISHED = 1, 2, 4  # tgms_cut_batch; with FEAS_NONFINITE
 
 # Every symbol include/tgms.h declares (checked by tests/test_capi_symbols.py).
 EXPORTS = [
@@ -51,6 +52,7 @@ EXPORTS = [
     "tgms_dilate_batch", "tgms_dilate_batch_device",
     "tgms_corridor_batch", "tgms_corridor_batch_device",
     "tgms_corridor_split_batch", "tgms_corridor_split_batch_device",
+    "tgms_cut_batch", "tgms_cut_batch_device",
 ]
 
 SCHED_REFINE, SCHED_END_DERIVS, SCHED_COEFFS, SCHED_STATUS, SCHED_COST, SCHED_SELF_GATHER = 1, 2, 4, 8, 16, 32
@@ -208,6 +210,10 @@ def load(path: str = ""):
     L.tgms_corridor_split_batch.argtypes = [vp, i32, vp, vp, vp, vp, ctypes.c_int64, vp, vp, vp, vp, dbl,
                                             ctypes.c_int, dbl, vp, vp, vp, vp, vp, vp, vp, vp]
     L.tgms_corridor_split_batch.restype = ctypes.c_int
+    L.tgms_cut_batch_device.argtypes = [vp, i32, vp, vp, vp, vp, vp, vp, dbl, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+    L.tgms_cut_batch_device.restype = ctypes.c_int
+    L.tgms_cut_batch.argtypes = [vp, i32, vp, vp, vp, vp, vp, vp, dbl, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+    L.tgms_cut_batch.restype = ctypes.c_int
     if L.tgms_abi_version() != ABI_VERSION:
         raise ImportError(f"libtgms ABI {L.tgms_abi_version()} != {ABI_VERSION}")
     _lib = L

@@ -65,7 +65,8 @@ struct tgms_handle {
     double* d_loop_ws = nullptr;
     size_t loop_ws_cap = 0;
     // tgms_neighbors_batch_device's per-vehicle boxes and knots, also tgms_clearance_batch_device's
-    // and the per-trajectory plan of tgms_corridor_split_batch_device (grow-only, ordered by scratch_ev)
+    // and the per-trajectory plans of tgms_corridor_split_batch_device and tgms_cut_batch_device
+    // (grow-only, ordered by scratch_ev)
     void* d_nbr_ws = nullptr;
     size_t nbr_ws_cap = 0;
     // ragged plans: the per-M group launches fork onto these streams and join back, so
@@ -2317,6 +2318,114 @@ tgms_status tgms_corridor_split_batch(tgms_handle* h, int32_t B, const int32_t* 
     if (F1) std::memcpy(faces_out, p + oF, F1 * 4 * sizeof(double));
     if (face_offsets) std::memcpy(face_offsets_out, p + oFo, (S1 + 1) * sizeof(int64_t));
     if (parent) std::memcpy(parent, p + oPar, S1 * sizeof(int32_t));
+    if (flags) std::memcpy(flags, p + oFl, n * sizeof(int32_t));
+    return TGMS_OK;
+}
+
+// ---- replan cut: restart each trajectory from its state at a given time ----
+
+// The argument rules the two cut entry points share (include/tgms.h).
+static tgms_status check_cut(tgms_handle* h, int32_t B, double min_frac, const void* so_out, const void* W_out,
+                             const void* T_out, const void* ED_out, const void* totals) {
+    if (B < 0) return set_err(h, TGMS_ERR_INVALID_ARG, "bad B");
+    if (!std::isfinite(min_frac) || !(min_frac >= 0.0) || !(min_frac < 1.0))
+        return set_err(h, TGMS_ERR_INVALID_ARG, "min_frac must be finite, >= 0 and < 1");
+    if (!so_out || !totals) return set_err(h, TGMS_ERR_INVALID_ARG, "seg_offsets_out or totals is NULL");
+    if (B > 0 && (!W_out || !T_out || !ED_out))
+        return set_err(h, TGMS_ERR_INVALID_ARG, "waypoints_out, seg_times_out or end_derivs_out is NULL");
+    return TGMS_OK;
+}
+
+// The launches of both calls, on the handle's scratch between acquire and release.
+static tgms_status cut_on_device(tgms_handle* h, int32_t B, const int32_t* d_so, const double* dW, const double* dT,
+                                 const double* dED, const double* dC, const double* d_t_cut, double min_frac,
+                                 int32_t* d_so_out, double* dW_out, double* dT_out, double* dED_out, double* dC_out,
+                                 int32_t* d_parent, double* d_t0, int64_t* d_totals, int32_t* d_flags,
+                                 hipStream_t st) {
+    tgms_status s = no_capture(h, st, "tgms_cut_batch_device");
+    if (s != TGMS_OK) return s;
+    TGMS_HIP(h, hipSetDevice(h->device));
+    s = ensure_nbr_ws(h, tgms::cut_scratch_bytes(B));
+    if (s == TGMS_OK) s = scratch_acquire(h, st);
+    if (s != TGMS_OK) return s;
+    return scratch_release(h, st,
+                           hip_err(h, tgms::launch_cut(B, d_so, dW, dT, dED, dC, d_t_cut, min_frac, h->d_nbr_ws,
+                                                       d_so_out, dW_out, dT_out, dED_out, dC_out, d_parent, d_t0,
+                                                       d_totals, d_flags, st),
+                                   "launch_cut"));
+}
+
+tgms_status tgms_cut_batch_device(tgms_handle* h, int32_t B, const int32_t* d_so, const double* dW, const double* dT,
+                                  const double* dED, const double* dC, const double* d_t_cut, double min_frac,
+                                  int32_t* d_so_out, double* dW_out, double* dT_out, double* dED_out, double* dC_out,
+                                  int32_t* d_parent, double* d_t0, int64_t* d_totals, int32_t* d_flags,
+                                  void* stream) {
+    if (tgms_status e = enter(h, __func__); e != TGMS_OK) return e;
+    const tgms_status s = check_cut(h, B, min_frac, d_so_out, dW_out, dT_out, dED_out, d_totals);
+    if (s != TGMS_OK) return s;
+    if (B > 0 && (!d_so || !dW || !dT || !dC || !d_t_cut)) return set_err(h, TGMS_ERR_INVALID_ARG, "NULL device pointer");
+    TGMS_CHECK_ALIGNED(h, dW, dT, dED, dC, d_t_cut, dW_out, dT_out, dED_out, dC_out, d_t0, d_totals);
+    return cut_on_device(h, B, d_so, dW, dT, dED, dC, d_t_cut, min_frac, d_so_out, dW_out, dT_out, dED_out, dC_out,
+                         d_parent, d_t0, d_totals, d_flags, static_cast<hipStream_t>(stream));
+}
+
+tgms_status tgms_cut_batch(tgms_handle* h, int32_t B, const int32_t* so, const double* waypoints,
+                           const double* seg_times, const double* end_derivs, const double* coeffs,
+                           const double* t_cut, double min_frac, int32_t* so_out, double* waypoints_out,
+                           double* seg_times_out, double* end_derivs_out, double* coeffs_out, int32_t* parent,
+                           double* t0_out, int64_t* totals, int32_t* flags) {
+    if (tgms_status e = enter(h); e != TGMS_OK) return e;
+    tgms_status s = check_offsets(h, B, so, TGMS_MAX_SEGMENTS, nullptr, nullptr);
+    if (s != TGMS_OK) return s;
+    s = check_cut(h, B, min_frac, so_out, waypoints_out, seg_times_out, end_derivs_out, totals);
+    if (s != TGMS_OK) return s;
+    if (B == 0) {
+        so_out[0] = 0;
+        totals[0] = 0;
+        return TGMS_OK;
+    }
+    if (!waypoints || !seg_times || !coeffs || !t_cut) return set_err(h, TGMS_ERR_INVALID_ARG, "NULL pointer");
+    if (h->host) {
+        tgms::host::cut(B, so, waypoints, seg_times, end_derivs, coeffs, t_cut, min_frac, so_out, waypoints_out,
+                        seg_times_out, end_derivs_out, coeffs_out, parent, t0_out, totals, flags);
+        return TGMS_OK;
+    }
+    // one output region at the capacities of the header (S segments), every array 16-byte aligned
+    // inside it: one download, of which the first S' rows go to the caller
+    const size_t S = (size_t)so[B], n = (size_t)B;
+    auto up16 = [](size_t v) { return (v + 15) & ~size_t(15); };
+    const size_t oW = 0, oT = up16(oW + (S + n) * 3 * sizeof(double)), oE = up16(oT + S * sizeof(double)),
+                 oC = up16(oE + n * 18 * sizeof(double)), oT0 = up16(oC + (coeffs_out ? S * 24 * sizeof(double) : 0)),
+                 oTot = up16(oT0 + n * sizeof(double)), oSo = up16(oTot + sizeof(int64_t)),
+                 oPar = up16(oSo + (n + 1) * sizeof(int32_t)), oFl = up16(oPar + S * sizeof(int32_t)),
+                 all_bytes = oFl + n * sizeof(int32_t);
+    double *dW, *dT, *dED, *dC, *dCut;
+    int32_t* dSo;
+    char* dOut;
+    s = stage(h, {input(&dW, waypoints, (S + n) * 3), input(&dT, seg_times, S), input(&dED, end_derivs, n * 18),
+                  input(&dC, coeffs, S * 24), input(&dCut, t_cut, n), input(&dSo, so, n + 1),
+                  output(&dOut, all_bytes)});
+    if (s != TGMS_OK) return s;
+    s = cut_on_device(h, B, dSo, dW, dT, dED, dC, dCut, min_frac, reinterpret_cast<int32_t*>(dOut + oSo),
+                      reinterpret_cast<double*>(dOut + oW), reinterpret_cast<double*>(dOut + oT),
+                      reinterpret_cast<double*>(dOut + oE),
+                      coeffs_out ? reinterpret_cast<double*>(dOut + oC) : nullptr,
+                      reinterpret_cast<int32_t*>(dOut + oPar), reinterpret_cast<double*>(dOut + oT0),
+                      reinterpret_cast<int64_t*>(dOut + oTot), reinterpret_cast<int32_t*>(dOut + oFl), h->stream);
+    if (s != TGMS_OK) return s;
+    std::vector<char> all(all_bytes);
+    TGMS_HIP(h, fetch(h, all.data(), dOut, all.size()));
+    TGMS_HIP(h, hipStreamSynchronize(h->stream));
+    const char* p = all.data();
+    std::memcpy(totals, p + oTot, sizeof(int64_t));
+    const size_t S1 = (size_t)totals[0];
+    std::memcpy(so_out, p + oSo, (n + 1) * sizeof(int32_t));
+    std::memcpy(waypoints_out, p + oW, (S1 + n) * 3 * sizeof(double));
+    std::memcpy(seg_times_out, p + oT, S1 * sizeof(double));
+    std::memcpy(end_derivs_out, p + oE, n * 18 * sizeof(double));
+    if (coeffs_out) std::memcpy(coeffs_out, p + oC, S1 * 24 * sizeof(double));
+    if (parent) std::memcpy(parent, p + oPar, S1 * sizeof(int32_t));
+    if (t0_out) std::memcpy(t0_out, p + oT0, n * sizeof(double));
     if (flags) std::memcpy(flags, p + oFl, n * sizeof(int32_t));
     return TGMS_OK;
 }

@@ -29,68 +29,13 @@
 #include "tgms_corridor_split_core.h"
 #include "tgms_device.h"
 #include "tgms_internal.h"
+#include "tgms_seg_tile.h"
 
 namespace tgms {
 namespace {
 
-constexpr int TILE = 4;                         // trajectories of one wavefront
-constexpr int SEGS = TILE * TGMS_MAX_SEGMENTS;  // 64: one lane per segment
-static_assert(SEGS == W64, "the segments of a tile are one pass of the wavefront");
+using namespace seg_tile;  // TILE, SEGS, Tile, load_tile, lane_segment, lane_knot
 constexpr int SCAN = 256;  // entries of one workgroup of the scan (tests/test_gpu_split.py pins its seams)
-
-// Wave-uniform: the tile's trajectories, their segment counts (0: outside 1..16, nothing is
-// read) and lane bases.
-struct Tile {
-    int Mt[TILE], base[TILE + 1];
-    int64_t s0[TILE];
-    bool oob[TILE];  // a segment count outside 1..TGMS_MAX_SEGMENTS
-};
-
-__device__ __forceinline__ void load_tile(const int32_t* __restrict__ so, int64_t b0, int nb, Tile& x) {
-    x.base[0] = 0;
-#pragma unroll
-    for (int t = 0; t < TILE; ++t) {
-        int M = 0;
-        x.s0[t] = 0;
-        x.oob[t] = false;
-        if (t < nb) {
-            const int32_t a = __builtin_amdgcn_readfirstlane(so[b0 + t]);
-            M = __builtin_amdgcn_readfirstlane(so[b0 + t + 1]) - a;
-            x.s0[t] = a;
-            x.oob[t] = M < 1 || M > TGMS_MAX_SEGMENTS;
-        }
-        x.Mt[t] = (M < 1 || M > TGMS_MAX_SEGMENTS) ? 0 : M;
-        x.base[t + 1] = x.base[t] + x.Mt[t];
-    }
-}
-
-// This lane's segment: its trajectory in the tile, its first lane, its segment count, its row.
-__device__ __forceinline__ void lane_segment(const Tile& x, int lane, int& tr, int& sb, int& M, int64_t& gs) {
-    tr = 0;
-#pragma unroll
-    for (int t = 1; t < TILE; ++t) tr += lane >= x.base[t] ? 1 : 0;
-    sb = x.base[0];
-    M = x.Mt[0];
-    gs = x.s0[0] + lane;
-#pragma unroll
-    for (int t = 1; t < TILE; ++t) {
-        sb = tr == t ? x.base[t] : sb;
-        M = tr == t ? x.Mt[t] : M;
-        gs = tr == t ? x.s0[t] + (lane - x.base[t]) : gs;
-    }
-}
-
-// The knot of this lane's segment: the times of the trajectory's earlier segments added left
-// to right, the corridor call's prefix sum.
-__device__ __forceinline__ double lane_knot(double T, int sb, int li) {
-    double knot = 0.0;
-#pragma unroll
-    for (int j = 0; j < TGMS_MAX_SEGMENTS - 1; ++j) {
-        const double Tj = __shfl(T, std::min(sb + j, W64 - 1), W64);
-        knot = j < li ? knot + Tj : knot;
-    }
-    return knot;
-}
 
 __device__ __forceinline__ int wave_inclusive(int v, int lane) {
 #pragma unroll
@@ -483,6 +428,17 @@ Scratch layout(int32_t B, void* base) {
 
 size_t corridor_split_scratch_bytes(int32_t B) { return layout(B, nullptr).bytes; }
 
+size_t count_scan_blocks(int32_t B) { return ((size_t)std::max(B, 0) + SCAN - 1) / SCAN; }
+
+hipError_t launch_count_scan(int32_t B, const int32_t* cntS, int64_t* cntF, int64_t* sumS, int64_t* sumF,
+                             int64_t shared_F, int32_t* so_out, int64_t* totals, hipStream_t stream) {
+    const unsigned nblk = (unsigned)count_scan_blocks(B);
+    TGMS_LAUNCH(k_scan_sums, dim3(nblk), dim3(SCAN), 0, stream, B, cntS, cntF, sumS, sumF);
+    TGMS_LAUNCH(k_scan_top, dim3(1), dim3(SCAN), 0, stream, (int32_t)nblk, sumS, sumF, shared_F, B, so_out, totals);
+    TGMS_LAUNCH(k_scan_add, dim3(nblk), dim3(SCAN), 0, stream, B, cntS, cntF, sumS, sumF, so_out);
+    return hipSuccess;
+}
+
 hipError_t launch_corridor_split(int32_t B, const int32_t* seg_offsets, const double* W, const double* T,
                                  const double* C, int64_t F, const double* faces, const int64_t* face_offsets,
                                  const double* seg_rec, const int32_t* seg_face, double r, int mode, double min_frac,
@@ -497,13 +453,11 @@ hipError_t launch_corridor_split(int32_t B, const int32_t* seg_offsets, const do
     const Scratch s = layout(B, scratch);
     const int64_t tiles = ((int64_t)B + TILE - 1) / TILE;
     const unsigned blocks = (unsigned)std::min<int64_t>(tiles, 4096);
-    const unsigned nblk = (unsigned)(((int64_t)B + SCAN - 1) / SCAN);
     TGMS_LAUNCH(k_split_plan, dim3(blocks), dim3(W64), 0, stream, B, seg_offsets, W, T, C, F, face_offsets, seg_rec,
                 seg_face, r, s.cntS, s.cntF, s.mask, flags);
-    TGMS_LAUNCH(k_scan_sums, dim3(nblk), dim3(SCAN), 0, stream, B, s.cntS, s.cntF, s.sumS, s.sumF);
-    TGMS_LAUNCH(k_scan_top, dim3(1), dim3(SCAN), 0, stream, (int32_t)nblk, s.sumS, s.sumF, shared_F, B, so_out,
-                totals);
-    TGMS_LAUNCH(k_scan_add, dim3(nblk), dim3(SCAN), 0, stream, B, s.cntS, s.cntF, s.sumS, s.sumF, so_out);
+    if (const hipError_t e = launch_count_scan(B, s.cntS, s.cntF, s.sumS, s.sumF, shared_F, so_out, totals, stream);
+        e != hipSuccess)
+        return e;
     TGMS_LAUNCH(k_split_write, dim3(blocks), dim3(W64), 0, stream, B, seg_offsets, W, T, C, F, faces, face_offsets,
                 seg_rec, seg_face, r, mode, min_frac, s.mask, s.cntF, so_out, W_out, T_out, faces_out, fo_out,
                 parent);

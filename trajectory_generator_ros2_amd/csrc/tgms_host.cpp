@@ -29,6 +29,7 @@
 #include "tgms_clearance_core.h"
 #include "tgms_corridor_core.h"
 #include "tgms_corridor_split_core.h"
+#include "tgms_cut_core.h"
 #include "tgms_dilate_core.h"
 #include "tgms_neighbors_core.h"
 #include "tgms_separation_core.h"
@@ -683,6 +684,73 @@ void corridor_split(int32_t B, const int32_t* so, const double* W, const double*
     if (fo) fo_out[s_out] = f_out;
     totals[0] = s_out;
     totals[1] = fo ? f_out : F;
+}
+
+void cut(int32_t B, const int32_t* so, const double* W, const double* T, const double* ED, const double* C,
+         const double* t_cut, double min_frac, int32_t* so_out, double* W_out, double* T_out, double* ED_out,
+         double* C_out, int32_t* parent, double* t0_out, int64_t* totals, int32_t* flags) {
+    namespace ct = tgms::cut;
+    int64_t s_out = 0;  // the next segment row
+    so_out[0] = 0;
+    for (int32_t b = 0; b < B; ++b) {
+        const int64_t s0 = so[b];
+        const int M = so[b + 1] - so[b];
+        const double* Tb = T + s0;
+        const double* Wb = W + (s0 + b) * 3;
+        const double* Eb = ED ? ED + (int64_t)b * 18 : nullptr;
+        double chk = 0.0;
+        bool bad = !(t_cut[b] == t_cut[b]);
+        for (int i = 0; i < M; ++i) {
+            chk = tgms::split::finite_chk(Tb[i], chk);
+            bad = bad || !(Tb[i] > 0.0);
+        }
+        for (int q = 0; q < M * 24; ++q) chk = tgms::split::finite_chk(C[s0 * 24 + q], chk);
+        for (int q = 0; q < (M + 1) * 3; ++q) chk = tgms::split::finite_chk(Wb[q], chk);
+        for (int q = 0; Eb && q < 18; ++q) chk = tgms::split::finite_chk(Eb[q], chk);
+        bad = bad || chk != 0.0;
+        const ct::Plan p = ct::plan_row(M, Tb, t_cut[b], min_frac, bad);
+        if (flags) flags[b] = p.flags;
+        if (t0_out) t0_out[b] = p.t0;
+        double* Eo = ED_out + (int64_t)b * 18;
+        std::fill(Eo, Eo + 18, 0.0);
+        const int64_t w_out = s_out + b;  // the row of the first waypoint
+        if (p.kind == ct::FINISHED) {
+            const double* wM = Wb + M * 3;
+            T_out[s_out] = Tb[M - 1];
+            if (parent) parent[s_out] = (int32_t)(s0 + M - 1);
+            std::copy(wM, wM + 3, W_out + w_out * 3);
+            std::copy(wM, wM + 3, W_out + (w_out + 1) * 3);
+            if (C_out) {
+                std::fill(C_out + s_out * 24, C_out + (s_out + 1) * 24, 0.0);
+                for (int ax = 0; ax < 3; ++ax) C_out[s_out * 24 + ax * 8] = wM[ax];
+            }
+        } else {
+            const int s = p.s;
+            const bool inside = p.t_loc > 0.0;
+            if (Eb) std::copy(Eb + 9, Eb + 18, Eo + 9);
+            if (s == 0 && !inside) {
+                if (Eb) std::copy(Eb, Eb + 9, Eo);
+            } else {
+                double c[24], x[3], d[9];
+                ct::shift_row(C + (s0 + s) * 24, p.t_loc, c, x, d);
+                std::copy(d, d + 9, Eo);
+                if (inside) {
+                    std::copy(x, x + 3, W_out + w_out * 3);
+                    if (C_out) std::copy(c, c + 24, C_out + s_out * 24);
+                }
+            }
+            if (!inside) std::copy(Wb + s * 3, Wb + s * 3 + 3, W_out + w_out * 3);
+            std::copy(Wb + (s + 1) * 3, Wb + (M + 1) * 3, W_out + (w_out + 1) * 3);
+            T_out[s_out] = ct::first_time(Tb[s], p.t_loc);
+            std::copy(Tb + s + 1, Tb + M, T_out + s_out + 1);
+            if (C_out) std::copy(C + (s0 + s + (inside ? 1 : 0)) * 24, C + (s0 + M) * 24,
+                                 C_out + (s_out + (inside ? 1 : 0)) * 24);
+            for (int i = s; parent && i < M; ++i) parent[s_out + i - s] = (int32_t)(s0 + i);
+        }
+        s_out += p.M_out;
+        so_out[b + 1] = (int32_t)s_out;
+    }
+    totals[0] = s_out;
 }
 
 }  // namespace host

@@ -87,5 +87,12 @@ void corridor_split(int32_t B, const int32_t* so, const double* W, const double*
                     int mode, double min_frac, int32_t* so_out, double* W_out, double* T_out, double* faces_out,
                     int64_t* fo_out, int32_t* parent, int64_t* totals, int32_t* flags);
 
+// The replan cut (include/tgms.h tgms_cut_batch) of a whole batch, trajectory by trajectory: the
+// decisions of tgms_cut_core.h, so every integer, flag, time and t0 is the device's to the bit.
+// The offsets are valid (1..TGMS_MAX_SEGMENTS); ED, C_out, parent, t0_out and flags are nullable.
+void cut(int32_t B, const int32_t* so, const double* W, const double* T, const double* ED, const double* C,
+         const double* t_cut, double min_frac, int32_t* so_out, double* W_out, double* T_out, double* ED_out,
+         double* C_out, int32_t* parent, double* t0_out, int64_t* totals, int32_t* flags);
+
 }  // namespace host
 }  // namespace tgms

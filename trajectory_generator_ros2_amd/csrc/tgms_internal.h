@@ -179,6 +179,25 @@ hipError_t launch_corridor_split(int32_t B, const int32_t* seg_offsets, const do
                                  int64_t* fo_out, int32_t* parent, int64_t* totals, int32_t* flags,
                                  hipStream_t stream);
 
+// The split's prefix sums for the other compactions (tgms_cut.hip), launched from where they are:
+// so_out [B+1] = the exclusive int32 scan of cntS [B] with the total at [B], cntF [B] (int64)
+// scanned in place, totals [2] = both sums (totals[1] = shared_F when that is >= 0).  sumS and
+// sumF hold count_scan_blocks(B) entries each.  Three launches; B > 0.
+size_t count_scan_blocks(int32_t B);
+hipError_t launch_count_scan(int32_t B, const int32_t* cntS, int64_t* cntF, int64_t* sumS, int64_t* sumF,
+                             int64_t shared_F, int32_t* so_out, int64_t* totals, hipStream_t stream);
+
+// Replan cut (tgms_cut.hip): every trajectory restarted from its state at t_cut [B]; the new
+// offsets, waypoints, times, end derivatives, coefficients (nullable), parent rows (nullable), t0
+// [B] (nullable), totals [1] = S' and flags [B] (nullable).  ED NULL: rest to rest.  Five launches
+// on `stream`: the plan per tile of launch_corridor, launch_count_scan, the write; `scratch` holds
+// cut_scratch_bytes(B) bytes, 256-byte aligned.  B == 0 writes so_out[0] and the total.
+size_t cut_scratch_bytes(int32_t B);
+hipError_t launch_cut(int32_t B, const int32_t* seg_offsets, const double* W, const double* T, const double* ED,
+                      const double* C, const double* t_cut, double min_frac, void* scratch, int32_t* so_out,
+                      double* W_out, double* T_out, double* ED_out, double* C_out, int32_t* parent, double* t0_out,
+                      int64_t* totals, int32_t* flags, hipStream_t stream);
+
 // Continuous swarm separation (tgms_separation.hip): per pair the closest approach d_min t_min
 // into sep [P][TGMS_SEP_STRIDE] and flags [P] (either nullable); pairs NULL: every unordered
 // pair, decoded on the device.  A wavefront per tile of 16 pairs, one launch.

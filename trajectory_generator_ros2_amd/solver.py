@@ -273,6 +273,39 @@ class Solver:
             return so2, W2[:S2 + B], T2[:S2], fc, None, parent[:S2], flags
         return so2, W2[:S2 + B], T2[:S2], fc2[:F2], fo2[:S2 + 1], parent[:S2], flags
 
+    def cut(self, seg_offsets, waypoints, seg_times, coeffs, t_cut, min_frac: float = 0.1, end_derivs=None,
+            want_coeffs: bool = True):
+        """Replan cut (include/tgms.h tgms_cut_batch): every trajectory restarted from its state at
+        t_cut [B].  Returns the new batch trimmed to its S' segments: (seg_offsets' [B+1],
+        waypoints' [S'+B,3], seg_times' [S'], end_derivs' [B,18], coeffs' [S',3,8] (the tail without
+        a solve; None when want_coeffs is False), parent [S'], t0 [B], flags [B] of CUT_* bits)."""
+        so = np.ascontiguousarray(seg_offsets, dtype=np.int32)
+        W = np.ascontiguousarray(waypoints, dtype=np.float64).reshape(-1, 3)
+        T = np.ascontiguousarray(seg_times, dtype=np.float64).reshape(-1)
+        C = np.ascontiguousarray(coeffs, dtype=np.float64)
+        tc = np.ascontiguousarray(t_cut, dtype=np.float64).reshape(-1)
+        ED = None if end_derivs is None else np.ascontiguousarray(end_derivs, dtype=np.float64).reshape(-1, 18)
+        B = so.shape[0] - 1
+        S = int(so[-1]) if B > 0 else 0
+        if tc.shape[0] != B:
+            raise ValueError("t_cut must have one entry per trajectory")
+        so2 = np.zeros(B + 1, dtype=np.int32)
+        W2 = np.zeros((S + B, 3), dtype=np.float64)
+        T2 = np.zeros(S, dtype=np.float64)
+        ED2 = np.zeros((B, 18), dtype=np.float64)
+        C2 = np.zeros((S, 3, 8), dtype=np.float64) if want_coeffs else None
+        parent = np.zeros(S, dtype=np.int32)
+        t0 = np.zeros(B, dtype=np.float64)
+        totals = np.zeros(1, dtype=np.int64)
+        flags = np.zeros(B, dtype=np.int32)
+        st = self._L.tgms_cut_batch(self._h, B, _ptr(so), _ptr(W), _ptr(T), _ptr(ED), _ptr(C), _ptr(tc),
+                                    float(min_frac), _ptr(so2), _ptr(W2), _ptr(T2), _ptr(ED2), _ptr(C2), _ptr(parent),
+                                    _ptr(t0), _ptr(totals), _ptr(flags))
+        if st != _lib.OK:
+            raise TgmsError(st, self.last_error())
+        S2 = int(totals[0])
+        return so2, W2[:S2 + B], T2[:S2], ED2, None if C2 is None else C2[:S2], parent[:S2], t0, flags
+
     def corridor_loop(self, seg_offsets, waypoints, seg_times, faces, face_offsets, r: float, rounds: int,
                       mode: int = _lib.SPLIT_PULL, min_frac: float = 0.1, end_derivs=None):
         """The planner's loop on host arrays: solve, corridor, split, up to `rounds` times, stopping
@@ -526,6 +559,22 @@ class Solver:
             _ptr(d_faces), _ptr(d_face_offsets), _ptr(d_seg_rec), _ptr(d_seg_face), float(r), int(mode),
             float(min_frac), _ptr(d_seg_offsets_out), _ptr(d_waypoints_out), _ptr(d_seg_times_out), _ptr(d_faces_out),
             _ptr(d_face_offsets_out), _ptr(d_parent), _ptr(d_totals), _ptr(d_flags), ctypes.c_void_p(stream))
+        if st != _lib.OK:
+            raise TgmsError(st, self.last_error())
+
+    def cut_device(self, B: int, d_seg_offsets, d_waypoints, d_seg_times, d_coeffs, d_t_cut, min_frac: float,
+                   d_seg_offsets_out, d_waypoints_out, d_seg_times_out, d_end_derivs_out, d_totals,
+                   d_end_derivs=None, d_coeffs_out=None, d_parent=None, d_t0_out=None, d_flags=None,
+                   stream: int = 0) -> None:
+        """tgms_cut_batch_device: outputs sized as the inputs (d_seg_offsets_out [B+1] int32,
+        d_waypoints_out [S+B,3], d_seg_times_out [S], d_end_derivs_out [B,18], d_coeffs_out [S,3,8],
+        d_parent [S] int32, d_t0_out [B], d_totals [1] int64 = S', d_flags [B] int32).  Not
+        capturable: it grows handle scratch with B."""
+        st = self._L.tgms_cut_batch_device(
+            self._h, int(B), _ptr(d_seg_offsets), _ptr(d_waypoints), _ptr(d_seg_times), _ptr(d_end_derivs),
+            _ptr(d_coeffs), _ptr(d_t_cut), float(min_frac), _ptr(d_seg_offsets_out), _ptr(d_waypoints_out),
+            _ptr(d_seg_times_out), _ptr(d_end_derivs_out), _ptr(d_coeffs_out), _ptr(d_parent), _ptr(d_t0_out),
+            _ptr(d_totals), _ptr(d_flags), ctypes.c_void_p(stream))
         if st != _lib.OK:
             raise TgmsError(st, self.last_error())
 
