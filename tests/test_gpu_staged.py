@@ -1,7 +1,8 @@
 """The host-pointer entry points' staging (workspace layout, uploads, downloads, status
 fold), through the C ABI with ctypes so that optional arguments can be NULL: the Python
 wrappers always pass every output, so nothing else runs the "records only" / "flags only"
-downloads of the three checks or the status == NULL path of the solves.
+downloads of the checks, the omitted outputs of the multi-output calls or the status == NULL
+path of the solves.
 
 Every comparison is bit for bit: the same kernel on the same inputs, whichever outputs the
 caller asked for.  The shared batch is ragged with S = 19 segments (odd: every fp64 region
@@ -16,7 +17,9 @@ pytestmark = pytest.mark.gpu
 
 MS = (1, 3, 10, 2, 3)
 B = len(MS)
+S19 = sum(MS)
 DT = 0.05
+G = 9.80665
 
 
 def _p(a):
@@ -221,3 +224,225 @@ def test_sampler_staging(solver, batch, ed):
     solver.sample_device(B, dev[0], dev[1], dev[2], dev[3], DT, dev[4], d_out, d_end_derivs=dev[5] if ed else None)
     torch.cuda.synchronize()
     assert np.array_equal(d_out.cpu().numpy(), out, equal_nan=True)
+
+
+def test_pair_download_thrust(solver, batch):
+    from trajectory_generator_ros2_amd._lib import THRUST_STRIDE, ThrustLimits
+    so, W, T, ED, C = batch
+    lim = ThrustLimits(9.0, 10.5, 0.1)
+    _pair_calls(lambda rec, fl: solver._L.tgms_thrust_batch(solver._h, B, _p(so), _p(T), _p(C[False]), G,
+                                                            ctypes.byref(lim), _p(rec), _p(fl)), B, THRUST_STRIDE)
+
+
+# ---- the calls with more than two outputs: any of them may be NULL ----
+
+
+def _fresh(spec, names):
+    """The outputs `names` of spec (name -> (shape, dtype), in argument order) filled with a
+    sentinel (NaN / -7), None for the others."""
+    return {k: np.full(sh, np.nan if dt == np.float64 else -7, dt) if k in names else None for k, (sh, dt) in spec.items()}
+
+
+def _untouched(a):
+    return np.isnan(a).all() if a.dtype == np.float64 else (a == -7).all()
+
+
+def _subset_calls(call, spec, subsets, rows=None):
+    """call(outputs: name -> array or None) -> status, asked for every output and then for each
+    of `subsets`: an array asked for equals the full call's bit for bit.  rows(full) -> name ->
+    count gives the rows a trimmed call writes: those are compared, and every row behind them
+    still holds its sentinel."""
+    full = _fresh(spec, spec)
+    assert call(full) == 0
+    n = rows(full) if rows else {k: len(v) for k, v in full.items()}
+    for k, v in full.items():
+        assert not _untouched(v[:n[k]]) and _untouched(v[n[k]:]), k
+    for names in subsets:
+        part = _fresh(spec, names)
+        assert call(part) == 0, names
+        for k in names:
+            assert np.array_equal(part[k][:n[k]], full[k][:n[k]], equal_nan=True), (names, k)
+            assert _untouched(part[k][n[k]:]), (names, k)
+    return full
+
+
+def _alone_and_omitted(spec, omitted=True):
+    names = list(spec)
+    return [(k,) for k in names] + ([tuple(x for x in names if x != k) for k in names] if omitted else [])
+
+
+DILATE = dict(scale=((B,), np.float64), active=((B,), np.int32), flags=((B,), np.int32),
+              seg_times_out=((S19,), np.float64), coeffs_out=((S19, 3, 8), np.float64))
+
+
+def _dilate_call(solver, batch):
+    from trajectory_generator_ros2_amd._lib import ThrustLimits
+    so, W, T, ED, C = batch
+    lim = ThrustLimits(9.0, 10.5, 0.1)  # close around hover: every row is stretched
+    return lambda o: solver._L.tgms_dilate_batch(solver._h, B, _p(so), _p(T), _p(C[False]), G, None, ctypes.byref(lim),
+                                                 0.25, 100.0, *(_p(o[k]) for k in DILATE))
+
+
+def test_dilate_outputs_optional(solver, batch):
+    from trajectory_generator_ros2_amd._lib import DIL_FLAG_MASK, DIL_NONE
+    full = _subset_calls(_dilate_call(solver, batch), DILATE, _alone_and_omitted(DILATE, omitted=False))
+    assert (full["active"] != DIL_NONE).all() and (full["scale"] > 0.25).all() and not (full["flags"] & DIL_FLAG_MASK).any()
+    assert not np.array_equal(full["seg_times_out"], batch[2])
+
+
+def test_dilate_staging_equals_the_device_call(solver, batch):
+    import torch
+    from trajectory_generator_ros2_amd._lib import ThrustLimits
+    so, W, T, ED, C = batch
+    full = _fresh(DILATE, DILATE)
+    assert _dilate_call(solver, batch)(full) == 0
+    dev = {k: torch.tensor(v, device="cuda") for k, v in _fresh(DILATE, DILATE).items()}
+    solver.dilate_device(B, *(torch.tensor(a, device="cuda") for a in (so, T, C[False])), G, None,
+                         ThrustLimits(9.0, 10.5, 0.1), 0.25, 100.0, dev["scale"], dev["active"], dev["flags"],
+                         dev["seg_times_out"], dev["coeffs_out"])
+    torch.cuda.synchronize()
+    for k in DILATE:
+        assert np.array_equal(dev[k].cpu().numpy(), full[k], equal_nan=True), k
+
+
+CORRIDOR = dict(rec=((B, 2), np.float64), where=((B, 2), np.int32), seg_rec=((S19, 2), np.float64),
+                seg_face=((S19,), np.int32), flags=((B,), np.int32))
+WIDTH = 0.3  # of the split's box corridor: 10 of the 19 segments leave it, by 0.05 at the least
+
+
+def _corridor_call(solver, batch, faces, fo):
+    so, W, T, ED, C = batch
+    return lambda o: solver._L.tgms_corridor_batch(solver._h, B, _p(so), _p(T), _p(C[False]), len(faces), _p(faces), _p(fo),
+                                                   0.0, *(_p(o[k]) for k in CORRIDOR))
+
+
+def test_corridor_outputs_optional(solver, batch):
+    from trajectory_generator_ros2_amd import synthetic as S
+    so, W, T, ED, C = batch
+    faces, fo = S.box_corridor(so, W, WIDTH)
+    full = _subset_calls(_corridor_call(solver, batch, faces, fo), CORRIDOR, _alone_and_omitted(CORRIDOR))
+    assert np.isfinite(full["rec"]).all() and (full["seg_face"] >= fo[:-1]).all() and (full["seg_face"] < fo[1:]).all()
+
+
+NEAR = dict(near=((B, 2), np.float64), index=((B,), np.int32), count=((B,), np.int32), tested=((B,), np.int32),
+            flags=((B,), np.int32))
+R_MIN = 1e3  # above every distance: nothing is culled
+NEAR_SUBSETS = [("near",), ("index",), ("count",), ("flags",), ("tested", "flags")]
+
+
+def _tested_alone_is_refused(solver, call):
+    """`tested` alone is an argument error (include/tgms.h: one of the other four is needed)."""
+    from trajectory_generator_ros2_amd._lib import ERR_INVALID_ARG
+    part = _fresh(NEAR, ("tested",))
+    assert call(part) == ERR_INVALID_ARG and _untouched(part["tested"])
+    assert solver.last_error().endswith("all NULL")
+
+
+def _neighbors_call(solver, batch):
+    so, W, T, ED, C = batch
+    t0 = 0.25 * np.arange(B)
+    return lambda o: solver._L.tgms_neighbors_batch(solver._h, B, _p(so), _p(T), _p(C[False]), _p(t0), None, R_MIN,
+                                                    *(_p(o[k]) for k in NEAR))
+
+
+def test_neighbors_outputs_optional(solver, batch):
+    call = _neighbors_call(solver, batch)
+    full = _subset_calls(call, NEAR, NEAR_SUBSETS)
+    assert (full["tested"] == B - 1).all() and (full["count"] == B - 1).all() and np.isfinite(full["near"]).all()
+    _tested_alone_is_refused(solver, call)
+
+
+def test_neighbors_staging_equals_the_device_call(solver, batch):
+    import torch
+    so, W, T, ED, C = batch
+    full = _fresh(NEAR, NEAR)
+    assert _neighbors_call(solver, batch)(full) == 0
+    dev = {k: torch.tensor(v, device="cuda") for k, v in _fresh(NEAR, NEAR).items()}
+    solver.neighbors_device(B, *(torch.tensor(a, device="cuda") for a in (so, T, C[False])), R_MIN,
+                            torch.tensor(0.25 * np.arange(B), device="cuda"), None, dev["near"], dev["index"],
+                            dev["count"], dev["tested"], dev["flags"])
+    torch.cuda.synchronize()
+    for k in NEAR:
+        assert np.array_equal(dev[k].cpu().numpy(), full[k], equal_nan=True), k
+
+
+def test_clearance_outputs_optional(solver, batch):
+    so, W, T, ED, C = batch
+    boxes = np.array([[0.0, 0.0, 2.5, 0.0, 0.0, 2.5], [3.0, 3.0, 0.0, 4.0, 4.0, 1.0]])  # K = 2: a point and a box
+    call = lambda o: solver._L.tgms_clearance_batch(solver._h, B, _p(so), _p(T), _p(C[False]), len(boxes), _p(boxes), None,
+                                                    R_MIN, *(_p(o[k]) for k in NEAR))
+    full = _subset_calls(call, NEAR, NEAR_SUBSETS)
+    assert (full["tested"] == len(boxes)).all() and (full["count"] == len(boxes)).all() and np.isfinite(full["near"]).all()
+    _tested_alone_is_refused(solver, call)
+
+
+SPLIT_ARGS = ("seg_offsets_out", "waypoints_out", "seg_times_out", "faces_out", "face_offsets_out", "parent", "totals",
+              "flags")
+SPLIT_PULL = 0
+
+
+def _split_spec(F, shared):
+    """The outputs at the header's capacities (2 S segments, 2 F faces); shared mode has no face
+    outputs."""
+    spec = dict(seg_offsets_out=((B + 1,), np.int32), waypoints_out=((2 * S19 + B, 3), np.float64),
+                seg_times_out=((2 * S19,), np.float64), faces_out=((2 * F, 4), np.float64),
+                face_offsets_out=((2 * S19 + 1,), np.int64), parent=((2 * S19,), np.int32), totals=((2,), np.int64),
+                flags=((B,), np.int32))
+    return {k: v for k, v in spec.items() if not (shared and k in ("faces_out", "face_offsets_out"))}
+
+
+@pytest.mark.parametrize("shared", [False, True], ids=["per_segment", "shared"])
+def test_split_outputs_optional_and_trimmed(solver, batch, shared):
+    """Some but not all segments are split, so S < S' < 2 S: the rows behind S' (S' + B waypoints, F'
+    faces) keep their sentinel.  Shared mode: one box 0.5 inside the waypoints' bounding box."""
+    from trajectory_generator_ros2_amd import synthetic as S
+    so, W, T, ED, C = batch
+    if shared:
+        lo, hi = W.min(axis=0) + 0.5, W.max(axis=0) - 0.5
+        faces, fo = np.zeros((6, 4)), None
+        for ax in range(3):
+            faces[2 * ax, ax], faces[2 * ax, 3] = 1.0, hi[ax]
+            faces[2 * ax + 1, ax], faces[2 * ax + 1, 3] = -1.0, -lo[ax]
+    else:
+        faces, fo = S.box_corridor(so, W, WIDTH)
+    cor = _fresh(CORRIDOR, ("seg_rec", "seg_face"))
+    assert _corridor_call(solver, batch, faces, fo)(cor) == 0
+    spec = _split_spec(len(faces), shared)
+    call = lambda o: solver._L.tgms_corridor_split_batch(
+        solver._h, B, _p(so), _p(W), _p(T), _p(C[False]), len(faces), _p(faces), _p(fo), _p(cor["seg_rec"]),
+        _p(cor["seg_face"]), 0.0, SPLIT_PULL, 0.1, *(_p(o.get(k)) for k in SPLIT_ARGS))
+
+    def rows(full):
+        S2, F2 = (int(x) for x in full["totals"])
+        print("split: S' = %d, F' = %d" % (S2, F2))
+        assert S19 < S2 < 2 * S19 and S2 == full["seg_offsets_out"][-1]
+        return dict(seg_offsets_out=B + 1, waypoints_out=S2 + B, seg_times_out=S2, faces_out=F2, face_offsets_out=S2 + 1,
+                    parent=S2, totals=2, flags=B)
+
+    _subset_calls(call, spec, [tuple(k for k in spec if k not in omit) for omit in (("parent",), ("flags",), ("parent", "flags"))],
+                  rows)
+
+
+CUT = dict(seg_offsets_out=((B + 1,), np.int32), waypoints_out=((S19 + B, 3), np.float64),
+           seg_times_out=((S19,), np.float64), end_derivs_out=((B, 18), np.float64), coeffs_out=((S19, 3, 8), np.float64),
+           parent=((S19,), np.int32), t0_out=((B,), np.float64), totals=((1,), np.int64), flags=((B,), np.int32))
+CUT_OPTIONAL = ("coeffs_out", "parent", "t0_out", "flags")
+
+
+def test_cut_outputs_optional_and_trimmed(solver, batch):
+    """t_cut at 40 % of every duration drops segments, so S' < S: the rows behind S' keep their
+    sentinel."""
+    so, W, T, ED, C = batch
+    t_cut = 0.4 * np.add.reduceat(T, so[:-1])
+    call = lambda o: solver._L.tgms_cut_batch(solver._h, B, _p(so), _p(W), _p(T), None, _p(C[False]), _p(t_cut), 0.1,
+                                              *(_p(o[k]) for k in CUT))
+
+    def rows(full):
+        S2 = int(full["totals"][0])
+        print("cut: S' = %d" % S2)
+        assert 0 < S2 < S19 and S2 == full["seg_offsets_out"][-1]
+        return dict(seg_offsets_out=B + 1, waypoints_out=S2 + B, seg_times_out=S2, end_derivs_out=B, coeffs_out=S2,
+                    parent=S2, t0_out=B, totals=1, flags=B)
+
+    subsets = [tuple(k for k in CUT if k != o) for o in CUT_OPTIONAL] + [tuple(k for k in CUT if k not in CUT_OPTIONAL)]
+    _subset_calls(call, CUT, subsets, rows)

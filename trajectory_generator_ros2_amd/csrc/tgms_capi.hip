@@ -213,36 +213,75 @@ hipError_t fetch(tgms_handle* h, T* host, const T* dev, size_t n) {
     return hipMemcpyAsync(host, dev, n * sizeof(T), hipMemcpyDeviceToHost, h->stream);
 }
 
-// The two results of a check, fp64 records and int32 flags, in one region with the flags
-// right behind the records (no rounding between them), so that one copy fetches both.  The
-// caller may ask for either alone: the kernel then gets nullptr for the other.
-struct ResultPair {
-    double* rec;  // host destinations, at most one of them NULL
-    int32_t* flags;
-    size_t n_rec, n_flags;  // elements
+// The outputs of a host-pointer call, one behind the other in one region so that one copy
+// fetches them all.  The call declares them in layout order with add(), stages the region as
+// one output(), launches with the typed device pointers dev() and downloads.  Every part
+// starts 16-byte aligned (the region itself 256-byte, by stage()); a part without elements or
+// one that is not reserved takes no space and has a NULL device pointer.
+struct Outputs {
+    template <class T>
+    struct Part {  // add()'s ticket: it carries the element type to dev() and take()
+        size_t i;
+    };
+    struct Slot {
+        void* host;  // the caller's destination; NULL: not asked for, or nothing reserved
+        size_t off, bytes;
+    };
+    std::vector<Slot> slots;
+    size_t bytes = 0;
     char* d = nullptr;      // the region (stage)
-    size_t rec_bytes() const { return n_rec * sizeof(double); }
-    size_t flag_bytes() const { return n_flags * sizeof(int32_t); }
-    double* d_rec() const { return rec ? reinterpret_cast<double*>(d) : nullptr; }
-    int32_t* d_flags() const { return flags ? reinterpret_cast<int32_t*>(d + rec_bytes()) : nullptr; }
-};
-Region output(ResultPair* p) { return output(&p->d, p->rec_bytes() + p->flag_bytes()); }
+    std::vector<char> all;  // its downloaded bytes (fetch)
 
-// Downloads what the caller asked for and waits for it.
-tgms_status download(tgms_handle* h, const ResultPair& p) {
-    if (p.rec && p.flags) {  // both in one copy, split on the host
-        std::vector<char> both(p.rec_bytes() + p.flag_bytes());
-        TGMS_HIP(h, fetch(h, both.data(), p.d, both.size()));
+    // `cap` elements for `host` (may be NULL); `reserve`: whether the device array exists, by
+    // default only when the caller asked for it (the kernel gets nullptr otherwise).
+    template <class T>
+    Part<T> add(T* host, size_t cap, bool reserve) {
+        const size_t n = reserve ? cap * sizeof(T) : 0, off = (bytes + 15) & ~size_t(15);
+        if (n) bytes = off + n;
+        slots.push_back({n ? host : nullptr, off, n});
+        return {slots.size() - 1};
+    }
+    template <class T>
+    Part<T> add(T* host, size_t cap) {
+        return add(host, cap, host != nullptr);
+    }
+    template <class T>
+    T* dev(Part<T> p) const {
+        return slots[p.i].bytes ? reinterpret_cast<T*>(d + slots[p.i].off) : nullptr;
+    }
+
+    // One copy out of the region and the wait for it.
+    tgms_status copy(tgms_handle* h, void* dst, size_t off, size_t n) const {
+        TGMS_HIP(h, hipMemcpyAsync(dst, d + off, n, hipMemcpyDeviceToHost, h->stream));
         TGMS_HIP(h, hipStreamSynchronize(h->stream));
-        std::memcpy(p.rec, both.data(), p.rec_bytes());
-        std::memcpy(p.flags, both.data() + p.rec_bytes(), p.flag_bytes());
         return TGMS_OK;
     }
-    if (p.rec) TGMS_HIP(h, fetch(h, p.rec, p.d_rec(), p.n_rec));
-    if (p.flags) TGMS_HIP(h, fetch(h, p.flags, p.d_flags(), p.n_flags));
-    TGMS_HIP(h, hipStreamSynchronize(h->stream));
-    return TGMS_OK;
-}
+    // The whole region; then take() hands the first n elements of a part to the caller if asked for.
+    tgms_status fetch(tgms_handle* h) {
+        all.resize(bytes);
+        return copy(h, all.data(), 0, bytes);
+    }
+    template <class T>
+    void take(Part<T> p, size_t n) const {
+        if (slots[p.i].host) std::memcpy(slots[p.i].host, all.data() + slots[p.i].off, n * sizeof(T));
+    }
+    // Every part the caller asked for, whole; a part asked for alone goes straight to the caller.
+    tgms_status download(tgms_handle* h) {
+        const Slot* only = nullptr;
+        int wanted = 0;
+        for (const Slot& s : slots)
+            if (s.host) {
+                only = &s;
+                ++wanted;
+            }
+        if (wanted == 1) return copy(h, only->host, only->off, only->bytes);
+        const tgms_status st = fetch(h);
+        for (const Slot& s : slots)
+            if (st == TGMS_OK && s.host) std::memcpy(s.host, all.data() + s.off, s.bytes);
+        return st;
+    }
+};
+Region output(Outputs* o) { return output(&o->d, o->bytes); }
 
 // The worst per-trajectory status of a batch; `message`: the first trajectory that has it
 // goes into last_error.
@@ -340,6 +379,21 @@ tgms_status ensure_nbr_ws(tgms_handle* h, size_t bytes) {
     TGMS_HIP(h, hipMalloc(&h->d_nbr_ws, bytes));
     h->nbr_ws_cap = bytes;
     return TGMS_OK;
+}
+
+// The launches of a call that uses `bytes` of the handle's scratch (d_nbr_ws), between acquire
+// and release: launch(scratch) -> hipError_t.  `entry` names the call where a capture is
+// refused, `where` the launch in last_error; a failed launch is still released.
+template <class Launch>
+tgms_status launch_on_scratch(tgms_handle* h, hipStream_t st, const char* entry, const char* where, size_t bytes,
+                              Launch launch) {
+    tgms_status s = no_capture(h, st, entry);
+    if (s != TGMS_OK) return s;
+    TGMS_HIP(h, hipSetDevice(h->device));
+    s = ensure_nbr_ws(h, bytes);
+    if (s == TGMS_OK) s = scratch_acquire(h, st);
+    if (s != TGMS_OK) return s;
+    return scratch_release(h, st, hip_err(h, launch(h->d_nbr_ws), where));
 }
 
 // The device-side grouping of the refinement loop: the permutation buffer (shared with the
@@ -1896,12 +1950,14 @@ tgms_status tgms_extrema_batch(tgms_handle* h, int32_t B, const int32_t* so, con
     const size_t S = (size_t)so[B];
     double *dW, *dT, *dED, *dC;
     int32_t* dSo;
-    ResultPair res{extrema, flags, (size_t)B * TGMS_EXTREMA_STRIDE, (size_t)B};  // 80 B + 4 B per trajectory
+    Outputs out;
+    const auto oRec = out.add(extrema, (size_t)B * TGMS_EXTREMA_STRIDE);
+    const auto oFl = out.add(flags, (size_t)B);
     s = stage(h, {input(&dW, waypoints, (S + B) * 3), input(&dT, seg_times, S), input(&dED, end_derivs, (size_t)B * 18),
-                  input(&dC, coeffs, S * 24), input(&dSo, so, (size_t)B + 1), output(&res)});
+                  input(&dC, coeffs, S * 24), input(&dSo, so, (size_t)B + 1), output(&out)});
     if (s != TGMS_OK) return s;
-    TGMS_HIP(h, tgms::launch_extrema(B, dSo, dW, dT, dED, dC, dt, lim, res.d_rec(), res.d_flags(), h->stream));
-    return download(h, res);
+    TGMS_HIP(h, tgms::launch_extrema(B, dSo, dW, dT, dED, dC, dt, lim, out.dev(oRec), out.dev(oFl), h->stream));
+    return out.download(h);
 }
 
 // ---- continuous feasibility bounds: the same record and flags, no dt ----
@@ -1944,11 +2000,13 @@ tgms_status tgms_bounds_batch(tgms_handle* h, int32_t B, const int32_t* so, cons
     const size_t S = (size_t)so[B];
     double *dT, *dC;
     int32_t* dSo;
-    ResultPair res{extrema, flags, (size_t)B * TGMS_EXTREMA_STRIDE, (size_t)B};  // 80 B + 4 B per trajectory
-    s = stage(h, {input(&dT, seg_times, S), input(&dC, coeffs, S * 24), input(&dSo, so, (size_t)B + 1), output(&res)});
+    Outputs out;
+    const auto oRec = out.add(extrema, (size_t)B * TGMS_EXTREMA_STRIDE);
+    const auto oFl = out.add(flags, (size_t)B);
+    s = stage(h, {input(&dT, seg_times, S), input(&dC, coeffs, S * 24), input(&dSo, so, (size_t)B + 1), output(&out)});
     if (s != TGMS_OK) return s;
-    TGMS_HIP(h, tgms::launch_bounds(B, dSo, dT, dC, lim, res.d_rec(), res.d_flags(), h->stream));
-    return download(h, res);
+    TGMS_HIP(h, tgms::launch_bounds(B, dSo, dT, dC, lim, out.dev(oRec), out.dev(oFl), h->stream));
+    return out.download(h);
 }
 
 // ---- continuous thrust and tilt bounds from differential flatness ----
@@ -2006,11 +2064,13 @@ tgms_status tgms_thrust_batch(tgms_handle* h, int32_t B, const int32_t* so, cons
     const size_t S = (size_t)so[B];
     double *dT, *dC;
     int32_t* dSo;
-    ResultPair res{rec, flags, (size_t)B * TGMS_THRUST_STRIDE, (size_t)B};  // 48 B + 4 B per trajectory
-    s = stage(h, {input(&dT, seg_times, S), input(&dC, coeffs, S * 24), input(&dSo, so, (size_t)B + 1), output(&res)});
+    Outputs out;
+    const auto oRec = out.add(rec, (size_t)B * TGMS_THRUST_STRIDE);
+    const auto oFl = out.add(flags, (size_t)B);
+    s = stage(h, {input(&dT, seg_times, S), input(&dC, coeffs, S * 24), input(&dSo, so, (size_t)B + 1), output(&out)});
     if (s != TGMS_OK) return s;
-    TGMS_HIP(h, tgms::launch_thrust(B, dSo, dT, dC, g, lim, res.d_rec(), res.d_flags(), h->stream));
-    return download(h, res);
+    TGMS_HIP(h, tgms::launch_thrust(B, dSo, dT, dC, g, lim, out.dev(oRec), out.dev(oFl), h->stream));
+    return out.download(h);
 }
 
 // ---- time dilation: the least uniform stretch that meets the dynamic limits ----
@@ -2089,32 +2149,18 @@ tgms_status tgms_dilate_batch(tgms_handle* h, int32_t B, const int32_t* so, cons
         }
         return TGMS_OK;
     }
-    // one output region, every array 16-byte aligned inside it: one download, split on the host
+    // the kernel gets nullptr for every output the caller omitted
     const size_t S = (size_t)so[B], n = (size_t)B;
-    auto up16 = [](size_t v) { return (v + 15) & ~size_t(15); };
-    const size_t oC = 0, oT = up16(oC + (coeffs_out ? S * 24 * sizeof(double) : 0)),
-                 oS = up16(oT + (seg_times_out ? S * sizeof(double) : 0)), oA = up16(oS + (scale ? n * sizeof(double) : 0)),
-                 oF = up16(oA + (active ? n * sizeof(int32_t) : 0)), all_bytes = oF + (flags ? n * sizeof(int32_t) : 0);
+    Outputs out;
+    const auto oC = out.add(coeffs_out, S * 24), oT = out.add(seg_times_out, S), oS = out.add(scale, n);
+    const auto oA = out.add(active, n), oF = out.add(flags, n);
     double *dT, *dC;
     int32_t* dSo;
-    char* dOut;
-    s = stage(h, {input(&dT, seg_times, S), input(&dC, coeffs, S * 24), input(&dSo, so, n + 1), output(&dOut, all_bytes)});
+    s = stage(h, {input(&dT, seg_times, S), input(&dC, coeffs, S * 24), input(&dSo, so, n + 1), output(&out)});
     if (s != TGMS_OK) return s;
-    TGMS_HIP(h, tgms::launch_dilate(B, dSo, dT, dC, g, lim, s_lo, s_hi, scale ? reinterpret_cast<double*>(dOut + oS) : nullptr,
-                                    active ? reinterpret_cast<int32_t*>(dOut + oA) : nullptr,
-                                    flags ? reinterpret_cast<int32_t*>(dOut + oF) : nullptr,
-                                    seg_times_out ? reinterpret_cast<double*>(dOut + oT) : nullptr,
-                                    coeffs_out ? reinterpret_cast<double*>(dOut + oC) : nullptr, h->stream));
-    std::vector<char> all(all_bytes);
-    TGMS_HIP(h, fetch(h, all.data(), dOut, all.size()));
-    TGMS_HIP(h, hipStreamSynchronize(h->stream));
-    const char* p = all.data();
-    if (coeffs_out) std::memcpy(coeffs_out, p + oC, S * 24 * sizeof(double));
-    if (seg_times_out) std::memcpy(seg_times_out, p + oT, S * sizeof(double));
-    if (scale) std::memcpy(scale, p + oS, n * sizeof(double));
-    if (active) std::memcpy(active, p + oA, n * sizeof(int32_t));
-    if (flags) std::memcpy(flags, p + oF, n * sizeof(int32_t));
-    return TGMS_OK;
+    TGMS_HIP(h, tgms::launch_dilate(B, dSo, dT, dC, g, lim, s_lo, s_hi, out.dev(oS), out.dev(oA), out.dev(oF), out.dev(oT),
+                                    out.dev(oC), h->stream));
+    return out.download(h);
 }
 
 // ---- corridor containment: worst excursion from per-segment polytopes ----
@@ -2162,34 +2208,20 @@ tgms_status tgms_corridor_batch(tgms_handle* h, int32_t B, const int32_t* so, co
         tgms::host::corridor(B, so, seg_times, coeffs, F, faces, face_offsets, r, rec, where, seg_rec, seg_face, flags);
         return TGMS_OK;
     }
-    // the fp64 rows first (per segment, then per trajectory), then the int32 rows one behind the
-    // other: one region, one download
+    // the kernel gets every array; what the caller omitted is dropped on the host
     const size_t S = (size_t)so[B], n = (size_t)B;
-    const size_t seg_bytes = S * TGMS_COR_STRIDE * sizeof(double), rec_bytes = n * TGMS_COR_STRIDE * sizeof(double);
-    const size_t all_bytes = seg_bytes + rec_bytes + (S + 3 * n) * sizeof(int32_t);
+    Outputs out;
+    const auto oSegRec = out.add(seg_rec, S * TGMS_COR_STRIDE, true), oRec = out.add(rec, n * TGMS_COR_STRIDE, true);
+    const auto oSegFace = out.add(seg_face, S, true), oWhere = out.add(where, 2 * n, true), oFl = out.add(flags, n, true);
     double *dT, *dC, *dF;
     int64_t* dFo;
     int32_t* dSo;
-    char* dOut;
     s = stage(h, {input(&dT, seg_times, S), input(&dC, coeffs, S * 24), input(&dF, faces, (size_t)F * 4),
-                  input(&dFo, face_offsets, S + 1), input(&dSo, so, n + 1), output(&dOut, all_bytes)});
+                  input(&dFo, face_offsets, S + 1), input(&dSo, so, n + 1), output(&out)});
     if (s != TGMS_OK) return s;
-    double* dSegRec = reinterpret_cast<double*>(dOut);
-    double* dRec = reinterpret_cast<double*>(dOut + seg_bytes);
-    int32_t* dI = reinterpret_cast<int32_t*>(dOut + seg_bytes + rec_bytes);  // seg_face [S], where [B][2], flags [B]
-    TGMS_HIP(h, tgms::launch_corridor(B, dSo, dT, dC, F, dF, dFo, r, dRec, dI + S, dSegRec, dI, dI + S + 2 * n,
-                                      h->stream));
-    std::vector<char> all(all_bytes);
-    TGMS_HIP(h, fetch(h, all.data(), dOut, all.size()));
-    TGMS_HIP(h, hipStreamSynchronize(h->stream));
-    const char* p = all.data();
-    if (seg_rec) std::memcpy(seg_rec, p, seg_bytes);
-    if (rec) std::memcpy(rec, p + seg_bytes, rec_bytes);
-    p += seg_bytes + rec_bytes;
-    if (seg_face) std::memcpy(seg_face, p, S * sizeof(int32_t));
-    if (where) std::memcpy(where, p + S * sizeof(int32_t), 2 * n * sizeof(int32_t));
-    if (flags) std::memcpy(flags, p + (S + 2 * n) * sizeof(int32_t), n * sizeof(int32_t));
-    return TGMS_OK;
+    TGMS_HIP(h, tgms::launch_corridor(B, dSo, dT, dC, F, dF, dFo, r, out.dev(oRec), out.dev(oWhere), out.dev(oSegRec),
+                                      out.dev(oSegFace), out.dev(oFl), h->stream));
+    return out.download(h);
 }
 
 // ---- corridor split: insert waypoints at the worst excursions ----
@@ -2216,27 +2248,6 @@ static tgms_status check_split(tgms_handle* h, int32_t B, int64_t F, const void*
     return TGMS_OK;
 }
 
-// The launches of both calls, on the handle's scratch between acquire and release.
-static tgms_status split_on_device(tgms_handle* h, int32_t B, const int32_t* d_so, const double* dW, const double* dT,
-                                   const double* dC, int64_t F, const double* d_faces, const int64_t* d_fo,
-                                   const double* d_seg_rec, const int32_t* d_seg_face, double r, int mode,
-                                   double min_frac, int32_t* d_so_out, double* dW_out, double* dT_out,
-                                   double* d_faces_out, int64_t* d_fo_out, int32_t* d_parent, int64_t* d_totals,
-                                   int32_t* d_flags, hipStream_t st) {
-    tgms_status s = no_capture(h, st, "tgms_corridor_split_batch_device");
-    if (s != TGMS_OK) return s;
-    TGMS_HIP(h, hipSetDevice(h->device));
-    s = ensure_nbr_ws(h, tgms::corridor_split_scratch_bytes(B));
-    if (s == TGMS_OK) s = scratch_acquire(h, st);
-    if (s != TGMS_OK) return s;
-    return scratch_release(
-        h, st,
-        hip_err(h, tgms::launch_corridor_split(B, d_so, dW, dT, dC, F, d_faces, d_fo, d_seg_rec, d_seg_face, r, mode,
-                                               min_frac, h->d_nbr_ws, d_so_out, dW_out, dT_out, d_faces_out, d_fo_out,
-                                               d_parent, d_totals, d_flags, st),
-                "launch_corridor_split"));
-}
-
 tgms_status tgms_corridor_split_batch_device(tgms_handle* h, int32_t B, const int32_t* d_so, const double* dW,
                                              const double* dT, const double* dC, int64_t F, const double* d_faces,
                                              const int64_t* d_face_offsets, const double* d_seg_rec,
@@ -2252,9 +2263,12 @@ tgms_status tgms_corridor_split_batch_device(tgms_handle* h, int32_t B, const in
         return set_err(h, TGMS_ERR_INVALID_ARG, "NULL device pointer");
     TGMS_CHECK_ALIGNED(h, dW, dT, dC, d_faces, d_face_offsets, d_seg_rec, dW_out, dT_out, d_faces_out, d_fo_out,
                        d_totals);
-    return split_on_device(h, B, d_so, dW, dT, dC, F, d_faces, d_face_offsets, d_seg_rec, d_seg_face, r, mode,
-                           min_frac, d_so_out, dW_out, dT_out, d_faces_out, d_fo_out, d_parent, d_totals, d_flags,
-                           static_cast<hipStream_t>(stream));
+    const hipStream_t st = static_cast<hipStream_t>(stream);
+    return launch_on_scratch(h, st, __func__, "launch_corridor_split", tgms::corridor_split_scratch_bytes(B), [&](void* ws) {
+        return tgms::launch_corridor_split(B, d_so, dW, dT, dC, F, d_faces, d_face_offsets, d_seg_rec, d_seg_face, r, mode,
+                                           min_frac, ws, d_so_out, dW_out, dT_out, d_faces_out, d_fo_out, d_parent,
+                                           d_totals, d_flags, st);
+    });
 }
 
 tgms_status tgms_corridor_split_batch(tgms_handle* h, int32_t B, const int32_t* so, const double* waypoints,
@@ -2282,43 +2296,40 @@ tgms_status tgms_corridor_split_batch(tgms_handle* h, int32_t B, const int32_t* 
                                    parent, totals, flags);
         return TGMS_OK;
     }
-    // one output region at the capacities of the header (2 S segments, 2 F faces), every array
-    // 16-byte aligned inside it: one download, of which the first S' / F' rows go to the caller
-    const size_t S = (size_t)so[B], n = (size_t)B, nf = face_offsets ? 2 * (size_t)F : 0;
-    auto up16 = [](size_t v) { return (v + 15) & ~size_t(15); };
-    const size_t oW = 0, oT = up16(oW + (2 * S + n) * 3 * sizeof(double)), oF = up16(oT + 2 * S * sizeof(double)),
-                 oFo = up16(oF + nf * 4 * sizeof(double)),
-                 oTot = up16(oFo + (face_offsets ? (2 * S + 1) * sizeof(int64_t) : 0)),
-                 oSo = up16(oTot + 2 * sizeof(int64_t)), oPar = up16(oSo + (n + 1) * sizeof(int32_t)),
-                 oFl = up16(oPar + 2 * S * sizeof(int32_t)), all_bytes = oFl + n * sizeof(int32_t);
+    // the outputs at the capacities of the header (2 S segments, 2 F faces), of which the first
+    // S' / F' rows go to the caller; no face outputs in shared mode, every other array reaches
+    // the kernel
+    const size_t S = (size_t)so[B], n = (size_t)B;
+    const bool per_seg = face_offsets != nullptr;
+    Outputs out;
+    const auto oW = out.add(waypoints_out, (2 * S + n) * 3), oT = out.add(seg_times_out, 2 * S),
+               oF = out.add(faces_out, 2 * (size_t)F * 4, per_seg);
+    const auto oFo = out.add(face_offsets_out, 2 * S + 1, per_seg), oTot = out.add(totals, 2);
+    const auto oSo = out.add(so_out, n + 1), oPar = out.add(parent, 2 * S, true), oFl = out.add(flags, n, true);
     double *dW, *dT, *dC, *dF, *dRec;
     int64_t* dFo;
     int32_t *dSo, *dFace;
-    char* dOut;
     s = stage(h, {input(&dW, waypoints, (S + n) * 3), input(&dT, seg_times, S), input(&dC, coeffs, S * 24),
                   input(&dF, faces, (size_t)F * 4), input(&dFo, face_offsets, S + 1), input(&dRec, seg_rec, S * 2),
-                  input(&dSo, so, n + 1), input(&dFace, seg_face, S), output(&dOut, all_bytes)});
+                  input(&dSo, so, n + 1), input(&dFace, seg_face, S), output(&out)});
     if (s != TGMS_OK) return s;
-    s = split_on_device(h, B, dSo, dW, dT, dC, F, dF, dFo, dRec, dFace, r, mode, min_frac,
-                        reinterpret_cast<int32_t*>(dOut + oSo), reinterpret_cast<double*>(dOut + oW),
-                        reinterpret_cast<double*>(dOut + oT), nf ? reinterpret_cast<double*>(dOut + oF) : nullptr,
-                        face_offsets ? reinterpret_cast<int64_t*>(dOut + oFo) : nullptr,
-                        reinterpret_cast<int32_t*>(dOut + oPar), reinterpret_cast<int64_t*>(dOut + oTot),
-                        reinterpret_cast<int32_t*>(dOut + oFl), h->stream);
+    const size_t ws_bytes = tgms::corridor_split_scratch_bytes(B);
+    s = launch_on_scratch(h, h->stream, "tgms_corridor_split_batch_device", "launch_corridor_split", ws_bytes, [&](void* ws) {
+        return tgms::launch_corridor_split(B, dSo, dW, dT, dC, F, dF, dFo, dRec, dFace, r, mode, min_frac, ws, out.dev(oSo),
+                                           out.dev(oW), out.dev(oT), out.dev(oF), out.dev(oFo), out.dev(oPar),
+                                           out.dev(oTot), out.dev(oFl), h->stream);
+    });
+    if (s == TGMS_OK) s = out.fetch(h);
     if (s != TGMS_OK) return s;
-    std::vector<char> all(all_bytes);
-    TGMS_HIP(h, fetch(h, all.data(), dOut, all.size()));
-    TGMS_HIP(h, hipStreamSynchronize(h->stream));
-    const char* p = all.data();
-    std::memcpy(totals, p + oTot, 2 * sizeof(int64_t));
-    const size_t S1 = (size_t)totals[0], F1 = face_offsets ? (size_t)totals[1] : 0;
-    std::memcpy(so_out, p + oSo, (n + 1) * sizeof(int32_t));
-    std::memcpy(waypoints_out, p + oW, (S1 + n) * 3 * sizeof(double));
-    std::memcpy(seg_times_out, p + oT, S1 * sizeof(double));
-    if (F1) std::memcpy(faces_out, p + oF, F1 * 4 * sizeof(double));
-    if (face_offsets) std::memcpy(face_offsets_out, p + oFo, (S1 + 1) * sizeof(int64_t));
-    if (parent) std::memcpy(parent, p + oPar, S1 * sizeof(int32_t));
-    if (flags) std::memcpy(flags, p + oFl, n * sizeof(int32_t));
+    out.take(oTot, 2);
+    const size_t S1 = (size_t)totals[0], F1 = (size_t)totals[1];
+    out.take(oSo, n + 1);
+    out.take(oW, (S1 + n) * 3);
+    out.take(oT, S1);
+    out.take(oF, F1 * 4);
+    out.take(oFo, S1 + 1);
+    out.take(oPar, S1);
+    out.take(oFl, n);
     return TGMS_OK;
 }
 
@@ -2336,25 +2347,6 @@ static tgms_status check_cut(tgms_handle* h, int32_t B, double min_frac, const v
     return TGMS_OK;
 }
 
-// The launches of both calls, on the handle's scratch between acquire and release.
-static tgms_status cut_on_device(tgms_handle* h, int32_t B, const int32_t* d_so, const double* dW, const double* dT,
-                                 const double* dED, const double* dC, const double* d_t_cut, double min_frac,
-                                 int32_t* d_so_out, double* dW_out, double* dT_out, double* dED_out, double* dC_out,
-                                 int32_t* d_parent, double* d_t0, int64_t* d_totals, int32_t* d_flags,
-                                 hipStream_t st) {
-    tgms_status s = no_capture(h, st, "tgms_cut_batch_device");
-    if (s != TGMS_OK) return s;
-    TGMS_HIP(h, hipSetDevice(h->device));
-    s = ensure_nbr_ws(h, tgms::cut_scratch_bytes(B));
-    if (s == TGMS_OK) s = scratch_acquire(h, st);
-    if (s != TGMS_OK) return s;
-    return scratch_release(h, st,
-                           hip_err(h, tgms::launch_cut(B, d_so, dW, dT, dED, dC, d_t_cut, min_frac, h->d_nbr_ws,
-                                                       d_so_out, dW_out, dT_out, dED_out, dC_out, d_parent, d_t0,
-                                                       d_totals, d_flags, st),
-                                   "launch_cut"));
-}
-
 tgms_status tgms_cut_batch_device(tgms_handle* h, int32_t B, const int32_t* d_so, const double* dW, const double* dT,
                                   const double* dED, const double* dC, const double* d_t_cut, double min_frac,
                                   int32_t* d_so_out, double* dW_out, double* dT_out, double* dED_out, double* dC_out,
@@ -2365,8 +2357,11 @@ tgms_status tgms_cut_batch_device(tgms_handle* h, int32_t B, const int32_t* d_so
     if (s != TGMS_OK) return s;
     if (B > 0 && (!d_so || !dW || !dT || !dC || !d_t_cut)) return set_err(h, TGMS_ERR_INVALID_ARG, "NULL device pointer");
     TGMS_CHECK_ALIGNED(h, dW, dT, dED, dC, d_t_cut, dW_out, dT_out, dED_out, dC_out, d_t0, d_totals);
-    return cut_on_device(h, B, d_so, dW, dT, dED, dC, d_t_cut, min_frac, d_so_out, dW_out, dT_out, dED_out, dC_out,
-                         d_parent, d_t0, d_totals, d_flags, static_cast<hipStream_t>(stream));
+    const hipStream_t st = static_cast<hipStream_t>(stream);
+    return launch_on_scratch(h, st, __func__, "launch_cut", tgms::cut_scratch_bytes(B), [&](void* ws) {
+        return tgms::launch_cut(B, d_so, dW, dT, dED, dC, d_t_cut, min_frac, ws, d_so_out, dW_out, dT_out, dED_out, dC_out,
+                                d_parent, d_t0, d_totals, d_flags, st);
+    });
 }
 
 tgms_status tgms_cut_batch(tgms_handle* h, int32_t B, const int32_t* so, const double* waypoints,
@@ -2390,43 +2385,35 @@ tgms_status tgms_cut_batch(tgms_handle* h, int32_t B, const int32_t* so, const d
                         seg_times_out, end_derivs_out, coeffs_out, parent, t0_out, totals, flags);
         return TGMS_OK;
     }
-    // one output region at the capacities of the header (S segments), every array 16-byte aligned
-    // inside it: one download, of which the first S' rows go to the caller
+    // the outputs at the capacities of the header (S segments), of which the first S' rows go to
+    // the caller; the kernel gets nullptr for omitted coefficients and every other array
     const size_t S = (size_t)so[B], n = (size_t)B;
-    auto up16 = [](size_t v) { return (v + 15) & ~size_t(15); };
-    const size_t oW = 0, oT = up16(oW + (S + n) * 3 * sizeof(double)), oE = up16(oT + S * sizeof(double)),
-                 oC = up16(oE + n * 18 * sizeof(double)), oT0 = up16(oC + (coeffs_out ? S * 24 * sizeof(double) : 0)),
-                 oTot = up16(oT0 + n * sizeof(double)), oSo = up16(oTot + sizeof(int64_t)),
-                 oPar = up16(oSo + (n + 1) * sizeof(int32_t)), oFl = up16(oPar + S * sizeof(int32_t)),
-                 all_bytes = oFl + n * sizeof(int32_t);
+    Outputs out;
+    const auto oW = out.add(waypoints_out, (S + n) * 3), oT = out.add(seg_times_out, S), oE = out.add(end_derivs_out, n * 18),
+               oC = out.add(coeffs_out, S * 24), oT0 = out.add(t0_out, n, true);
+    const auto oTot = out.add(totals, 1);
+    const auto oSo = out.add(so_out, n + 1), oPar = out.add(parent, S, true), oFl = out.add(flags, n, true);
     double *dW, *dT, *dED, *dC, *dCut;
     int32_t* dSo;
-    char* dOut;
     s = stage(h, {input(&dW, waypoints, (S + n) * 3), input(&dT, seg_times, S), input(&dED, end_derivs, n * 18),
-                  input(&dC, coeffs, S * 24), input(&dCut, t_cut, n), input(&dSo, so, n + 1),
-                  output(&dOut, all_bytes)});
+                  input(&dC, coeffs, S * 24), input(&dCut, t_cut, n), input(&dSo, so, n + 1), output(&out)});
     if (s != TGMS_OK) return s;
-    s = cut_on_device(h, B, dSo, dW, dT, dED, dC, dCut, min_frac, reinterpret_cast<int32_t*>(dOut + oSo),
-                      reinterpret_cast<double*>(dOut + oW), reinterpret_cast<double*>(dOut + oT),
-                      reinterpret_cast<double*>(dOut + oE),
-                      coeffs_out ? reinterpret_cast<double*>(dOut + oC) : nullptr,
-                      reinterpret_cast<int32_t*>(dOut + oPar), reinterpret_cast<double*>(dOut + oT0),
-                      reinterpret_cast<int64_t*>(dOut + oTot), reinterpret_cast<int32_t*>(dOut + oFl), h->stream);
+    s = launch_on_scratch(h, h->stream, "tgms_cut_batch_device", "launch_cut", tgms::cut_scratch_bytes(B), [&](void* ws) {
+        return tgms::launch_cut(B, dSo, dW, dT, dED, dC, dCut, min_frac, ws, out.dev(oSo), out.dev(oW), out.dev(oT),
+                                out.dev(oE), out.dev(oC), out.dev(oPar), out.dev(oT0), out.dev(oTot), out.dev(oFl), h->stream);
+    });
+    if (s == TGMS_OK) s = out.fetch(h);
     if (s != TGMS_OK) return s;
-    std::vector<char> all(all_bytes);
-    TGMS_HIP(h, fetch(h, all.data(), dOut, all.size()));
-    TGMS_HIP(h, hipStreamSynchronize(h->stream));
-    const char* p = all.data();
-    std::memcpy(totals, p + oTot, sizeof(int64_t));
+    out.take(oTot, 1);
     const size_t S1 = (size_t)totals[0];
-    std::memcpy(so_out, p + oSo, (n + 1) * sizeof(int32_t));
-    std::memcpy(waypoints_out, p + oW, (S1 + n) * 3 * sizeof(double));
-    std::memcpy(seg_times_out, p + oT, S1 * sizeof(double));
-    std::memcpy(end_derivs_out, p + oE, n * 18 * sizeof(double));
-    if (coeffs_out) std::memcpy(coeffs_out, p + oC, S1 * 24 * sizeof(double));
-    if (parent) std::memcpy(parent, p + oPar, S1 * sizeof(int32_t));
-    if (t0_out) std::memcpy(t0_out, p + oT0, n * sizeof(double));
-    if (flags) std::memcpy(flags, p + oFl, n * sizeof(int32_t));
+    out.take(oSo, n + 1);
+    out.take(oW, (S1 + n) * 3);
+    out.take(oT, S1);
+    out.take(oE, n * 18);
+    out.take(oC, S1 * 24);
+    out.take(oPar, S1);
+    out.take(oT0, n);
+    out.take(oFl, n);
     return TGMS_OK;
 }
 
@@ -2509,12 +2496,14 @@ tgms_status tgms_separation_batch(tgms_handle* h, int32_t B, const int32_t* so, 
     const size_t S = (size_t)so[B];
     double *dT, *dC, *dT0;
     int32_t *dSo, *dP;
-    ResultPair res{sep, flags, (size_t)P * TGMS_SEP_STRIDE, (size_t)P};  // 16 B + 4 B per pair
+    Outputs out;
+    const auto oSep = out.add(sep, (size_t)P * TGMS_SEP_STRIDE);
+    const auto oFl = out.add(flags, (size_t)P);
     s = stage(h, {input(&dT, seg_times, S), input(&dC, coeffs, S * 24), input(&dT0, start_times, (size_t)B),
-                  input(&dSo, so, (size_t)B + 1), input(&dP, pairs, (size_t)P * 2), output(&res)});
+                  input(&dSo, so, (size_t)B + 1), input(&dP, pairs, (size_t)P * 2), output(&out)});
     if (s != TGMS_OK) return s;
-    TGMS_HIP(h, tgms::launch_separation(B, dSo, dT, dC, dT0, P, dP, sc, r_min, res.d_rec(), res.d_flags(), h->stream));
-    return download(h, res);
+    TGMS_HIP(h, tgms::launch_separation(B, dSo, dT, dC, dT0, P, dP, sc, r_min, out.dev(oSep), out.dev(oFl), h->stream));
+    return out.download(h);
 }
 
 // ---- swarm neighbour search: nearest vehicle per vehicle, far pairs culled ----
@@ -2530,22 +2519,6 @@ static tgms_status check_neighbors(tgms_handle* h, int32_t B, const double* scal
     return TGMS_OK;
 }
 
-// The launches of both calls, on the handle's scratch between acquire and release.
-static tgms_status neighbors_on_device(tgms_handle* h, int32_t B, const int32_t* d_so, const double* dT,
-                                       const double* dC, const double* dT0, const double (&sc)[3], double r_min,
-                                       double* d_near, int32_t* d_nbr, int32_t* d_count, int32_t* d_tested,
-                                       int32_t* d_flags, hipStream_t st) {
-    tgms_status s = no_capture(h, st, "tgms_neighbors_batch_device");
-    if (s != TGMS_OK) return s;
-    TGMS_HIP(h, hipSetDevice(h->device));
-    s = ensure_nbr_ws(h, tgms::neighbors_scratch_bytes(B));
-    if (s == TGMS_OK) s = scratch_acquire(h, st);
-    if (s != TGMS_OK) return s;
-    return scratch_release(h, st, hip_err(h, tgms::launch_neighbors(B, d_so, dT, dC, dT0, sc, r_min, h->d_nbr_ws, d_near,
-                                                                    d_nbr, d_count, d_tested, d_flags, st),
-                                          "launch_neighbors"));
-}
-
 tgms_status tgms_neighbors_batch_device(tgms_handle* h, int32_t B, const int32_t* d_so, const double* dT,
                                         const double* dC, const double* d_start_times, const double* scale,
                                         double r_min, double* d_near, int32_t* d_nbr, int32_t* d_count,
@@ -2557,8 +2530,11 @@ tgms_status tgms_neighbors_batch_device(tgms_handle* h, int32_t B, const int32_t
     if (B == 0) return TGMS_OK;
     if (!d_so || !dT || !dC) return set_err(h, TGMS_ERR_INVALID_ARG, "NULL device pointer");
     TGMS_CHECK_ALIGNED(h, dT, dC, d_start_times, d_near);
-    return neighbors_on_device(h, B, d_so, dT, dC, d_start_times, sc, r_min, d_near, d_nbr, d_count, d_tested, d_flags,
-                               static_cast<hipStream_t>(stream));
+    const hipStream_t st = static_cast<hipStream_t>(stream);
+    return launch_on_scratch(h, st, __func__, "launch_neighbors", tgms::neighbors_scratch_bytes(B), [&](void* ws) {
+        return tgms::launch_neighbors(B, d_so, dT, dC, d_start_times, sc, r_min, ws, d_near, d_nbr, d_count, d_tested,
+                                      d_flags, st);
+    });
 }
 
 tgms_status tgms_neighbors_batch(tgms_handle* h, int32_t B, const int32_t* so, const double* seg_times,
@@ -2576,26 +2552,23 @@ tgms_status tgms_neighbors_batch(tgms_handle* h, int32_t B, const int32_t* so, c
         tgms::host::neighbors(B, so, seg_times, coeffs, start_times, sc, r_min, near, nbr, count, tested, flags);
         return TGMS_OK;
     }
-    // the records first, then the four int32 rows one behind the other: one region, one download
-    const size_t S = (size_t)so[B], n = (size_t)B, rec_bytes = n * TGMS_SEP_STRIDE * sizeof(double);
+    // the kernel gets every array; what the caller omitted is dropped on the host
+    const size_t S = (size_t)so[B], n = (size_t)B;
+    Outputs out;
+    const auto oNear = out.add(near, n * TGMS_SEP_STRIDE, true);
+    const auto oNbr = out.add(nbr, n, true), oCnt = out.add(count, n, true), oTst = out.add(tested, n, true),
+               oFl = out.add(flags, n, true);
     double *dT, *dC, *dT0;
     int32_t* dSo;
-    char* dOut;
     s = stage(h, {input(&dT, seg_times, S), input(&dC, coeffs, S * 24), input(&dT0, start_times, n),
-                  input(&dSo, so, n + 1), output(&dOut, rec_bytes + 4 * n * sizeof(int32_t))});
+                  input(&dSo, so, n + 1), output(&out)});
     if (s != TGMS_OK) return s;
-    double* dNear = reinterpret_cast<double*>(dOut);
-    int32_t* dI = reinterpret_cast<int32_t*>(dOut + rec_bytes);
-    s = neighbors_on_device(h, B, dSo, dT, dC, dT0, sc, r_min, dNear, dI, dI + n, dI + 2 * n, dI + 3 * n, h->stream);
-    if (s != TGMS_OK) return s;
-    std::vector<char> all(rec_bytes + 4 * n * sizeof(int32_t));
-    TGMS_HIP(h, fetch(h, all.data(), dOut, all.size()));
-    TGMS_HIP(h, hipStreamSynchronize(h->stream));
-    if (near) std::memcpy(near, all.data(), rec_bytes);
-    int32_t* const dst[4] = {nbr, count, tested, flags};
-    for (int k = 0; k < 4; ++k)
-        if (dst[k]) std::memcpy(dst[k], all.data() + rec_bytes + k * n * sizeof(int32_t), n * sizeof(int32_t));
-    return TGMS_OK;
+    s = launch_on_scratch(h, h->stream, "tgms_neighbors_batch_device", "launch_neighbors", tgms::neighbors_scratch_bytes(B),
+                          [&](void* ws) {
+                              return tgms::launch_neighbors(B, dSo, dT, dC, dT0, sc, r_min, ws, out.dev(oNear), out.dev(oNbr),
+                                                            out.dev(oCnt), out.dev(oTst), out.dev(oFl), h->stream);
+                          });
+    return s != TGMS_OK ? s : out.download(h);
 }
 
 // ---- obstacle clearance: nearest static box per trajectory, far ones culled ----
@@ -2613,23 +2586,6 @@ static tgms_status check_clearance(tgms_handle* h, int32_t B, int32_t K, const d
     return TGMS_OK;
 }
 
-// The launches of both calls, on the handle's scratch (the neighbour search's buffer) between
-// acquire and release.
-static tgms_status clearance_on_device(tgms_handle* h, int32_t B, const int32_t* d_so, const double* dT,
-                                       const double* dC, int32_t K, const double* dOb, const double (&sc)[3],
-                                       double r_min, double* d_near, int32_t* d_obs, int32_t* d_count,
-                                       int32_t* d_tested, int32_t* d_flags, hipStream_t st) {
-    tgms_status s = no_capture(h, st, "tgms_clearance_batch_device");
-    if (s != TGMS_OK) return s;
-    TGMS_HIP(h, hipSetDevice(h->device));
-    s = ensure_nbr_ws(h, tgms::clearance_scratch_bytes(B, K));
-    if (s == TGMS_OK) s = scratch_acquire(h, st);
-    if (s != TGMS_OK) return s;
-    return scratch_release(h, st, hip_err(h, tgms::launch_clearance(B, d_so, dT, dC, K, dOb, sc, r_min, h->d_nbr_ws,
-                                                                    d_near, d_obs, d_count, d_tested, d_flags, st),
-                                          "launch_clearance"));
-}
-
 tgms_status tgms_clearance_batch_device(tgms_handle* h, int32_t B, const int32_t* d_so, const double* dT,
                                         const double* dC, int32_t K, const double* d_obstacles, const double* scale,
                                         double r_min, double* d_near, int32_t* d_obs, int32_t* d_count,
@@ -2641,8 +2597,11 @@ tgms_status tgms_clearance_batch_device(tgms_handle* h, int32_t B, const int32_t
     if (B == 0) return TGMS_OK;
     if (!d_so || !dT || !dC || (K > 0 && !d_obstacles)) return set_err(h, TGMS_ERR_INVALID_ARG, "NULL device pointer");
     TGMS_CHECK_ALIGNED(h, dT, dC, d_obstacles, d_near);
-    return clearance_on_device(h, B, d_so, dT, dC, K, d_obstacles, sc, r_min, d_near, d_obs, d_count, d_tested,
-                               d_flags, static_cast<hipStream_t>(stream));
+    const hipStream_t st = static_cast<hipStream_t>(stream);
+    return launch_on_scratch(h, st, __func__, "launch_clearance", tgms::clearance_scratch_bytes(B, K), [&](void* ws) {
+        return tgms::launch_clearance(B, d_so, dT, dC, K, d_obstacles, sc, r_min, ws, d_near, d_obs, d_count, d_tested,
+                                      d_flags, st);
+    });
 }
 
 tgms_status tgms_clearance_batch(tgms_handle* h, int32_t B, const int32_t* so, const double* seg_times,
@@ -2661,27 +2620,23 @@ tgms_status tgms_clearance_batch(tgms_handle* h, int32_t B, const int32_t* so, c
         tgms::host::clearance(B, so, seg_times, coeffs, K, obstacles, sc, r_min, near, obs, count, tested, flags);
         return TGMS_OK;
     }
-    // the records first, then the four int32 rows one behind the other: one region, one download
-    const size_t S = (size_t)so[B], n = (size_t)B, rec_bytes = n * TGMS_SEP_STRIDE * sizeof(double);
+    // the kernel gets every array; what the caller omitted is dropped on the host
+    const size_t S = (size_t)so[B], n = (size_t)B;
+    Outputs out;
+    const auto oNear = out.add(near, n * TGMS_SEP_STRIDE, true);
+    const auto oObs = out.add(obs, n, true), oCnt = out.add(count, n, true), oTst = out.add(tested, n, true),
+               oFl = out.add(flags, n, true);
     double *dT, *dC, *dOb;
     int32_t* dSo;
-    char* dOut;
     s = stage(h, {input(&dT, seg_times, S), input(&dC, coeffs, S * 24), input(&dOb, obstacles, (size_t)K * 6),
-                  input(&dSo, so, n + 1), output(&dOut, rec_bytes + 4 * n * sizeof(int32_t))});
+                  input(&dSo, so, n + 1), output(&out)});
     if (s != TGMS_OK) return s;
-    double* dNear = reinterpret_cast<double*>(dOut);
-    int32_t* dI = reinterpret_cast<int32_t*>(dOut + rec_bytes);
-    s = clearance_on_device(h, B, dSo, dT, dC, K, dOb, sc, r_min, dNear, dI, dI + n, dI + 2 * n, dI + 3 * n,
-                            h->stream);
-    if (s != TGMS_OK) return s;
-    std::vector<char> all(rec_bytes + 4 * n * sizeof(int32_t));
-    TGMS_HIP(h, fetch(h, all.data(), dOut, all.size()));
-    TGMS_HIP(h, hipStreamSynchronize(h->stream));
-    if (near) std::memcpy(near, all.data(), rec_bytes);
-    int32_t* const dst[4] = {obs, count, tested, flags};
-    for (int k = 0; k < 4; ++k)
-        if (dst[k]) std::memcpy(dst[k], all.data() + rec_bytes + k * n * sizeof(int32_t), n * sizeof(int32_t));
-    return TGMS_OK;
+    s = launch_on_scratch(h, h->stream, "tgms_clearance_batch_device", "launch_clearance",
+                          tgms::clearance_scratch_bytes(B, K), [&](void* ws) {
+                              return tgms::launch_clearance(B, dSo, dT, dC, K, dOb, sc, r_min, ws, out.dev(oNear), out.dev(oObs),
+                                                            out.dev(oCnt), out.dev(oTst), out.dev(oFl), h->stream);
+                          });
+    return s != TGMS_OK ? s : out.download(h);
 }
 
 // ---- multi-GPU ----
