@@ -44,7 +44,7 @@
  *     capture with no slab large enough) return TGMS_ERR_UNSUPPORTED while their stream is
  *     capturing.
  *     tgms_extrema_batch_device, tgms_bounds_batch_device, tgms_thrust_batch_device,
- *     tgms_dilate_batch_device and tgms_corridor_batch_device (one kernel, no plan, no scratch) may be captured for any
+ *     tgms_rate_batch_device, tgms_dilate_batch_device and tgms_corridor_batch_device (one kernel, no plan, no scratch) may be captured for any
  *     batch, ragged included;
  *   - there is no CPU fallback: with no usable GPU, tgms_create fails with
  *     TGMS_ERR_NO_DEVICE.  A GPU-less node asks for the host backend explicitly
@@ -116,7 +116,7 @@ tgms_status tgms_create(tgms_handle** out, int device);
 /* The explicit host backend (BASELINE config 1: a ROS 2 node with no GPU; the reference
  * generates on the executor thread's CPU, src/TrajectoryGenerator.cpp:54-57, :71).  A host
  * handle runs tgms_solve_batch (reduced method), tgms_sample_batch, tgms_extrema_batch,
- * tgms_bounds_batch, tgms_thrust_batch, tgms_dilate_batch, tgms_corridor_batch, tgms_corridor_split_batch, tgms_cut_batch, tgms_separation_batch, tgms_neighbors_batch and tgms_clearance_batch on the calling thread with the GPU path's conventions; every other entry point returns
+ * tgms_bounds_batch, tgms_thrust_batch, tgms_rate_batch, tgms_dilate_batch, tgms_corridor_batch, tgms_corridor_split_batch, tgms_cut_batch, tgms_separation_batch, tgms_neighbors_batch and tgms_clearance_batch on the calling thread with the GPU path's conventions; every other entry point returns
  * TGMS_ERR_UNSUPPORTED on it.  Chosen by the caller only: tgms_create never falls back to
  * it. */
 tgms_status tgms_create_host(tgms_handle** out);
@@ -515,9 +515,8 @@ tgms_status tgms_clearance_batch(tgms_handle* h, int32_t B, const int32_t* seg_o
  * is then the maximum over the candidates and carries no accuracy claim; TGMS_THRUST_LOW is
  * what catches such a trajectory.  fp64 evaluations at located candidates, not a certificate;
  * a touch of a derivative without a sign change may be skipped, as for the bounds.
- *   The body rate |f x p'''| / ||f||^2 is not computed (its stationary points are the roots of
- * a polynomial of degree 27); j_peak / f_min from the bounds and thrust records is a sound
- * upper bound.
+ *   The body rate |f x p'''| / ||f||^2 is tgms_rate_batch's (below); j_peak / f_min from the
+ * bounds and thrust records is a sound but loose upper bound of it.
  *   At least one of rec / flags must be non-NULL; fp64 device arrays are 16-byte aligned; B == 0
  * is TGMS_OK and launches nothing.  tgms_thrust_batch_device is one kernel launch with no host
  * plan and no handle scratch, so it may be captured into a HIP graph for any batch, ragged
@@ -542,6 +541,65 @@ tgms_status tgms_thrust_batch_device(tgms_handle* h, int32_t B, const int32_t* d
 tgms_status tgms_thrust_batch(tgms_handle* h, int32_t B, const int32_t* seg_offsets,
                               const double* seg_times, const double* coeffs, double g,
                               const tgms_thrust_limits* limits, double* rec, int32_t* flags);
+
+/* ---- continuous body-rate bound: peak roll/pitch rate from differential flatness ----
+ * What a multirotor's rate controller and gyros saturate on.  The thrust vector f(t) = p''(t) +
+ * g e_z fixes the body z axis f / ||f||, and that axis turns at
+ *     omega(t) = ||f x p'''|| / ||f||^2      (rad/s)
+ * the magnitude of the roll/pitch body rate (f' = p''' because g is constant).  The yaw-rate
+ * component about the body axis depends on the yaw plan and is NOT part of it.  j_peak / f_min
+ * from the bounds and thrust records bounds omega from above, but pairs the largest jerk anywhere
+ * with the lowest thrust anywhere and counts the jerk along f, which turns nothing.  Per
+ * trajectory one record of TGMS_RATE_STRIDE doubles
+ *     omega_max t_omega
+ * omega_max the maximum of omega over all segments' closed intervals, t_omega a time in [0, D_b]
+ * at which it is attained: a knot's left-to-right prefix sum of T plus the local time, clamped
+ * to D_b (the thrust call's rule); which one among ties is unspecified.  seg_rec, in the
+ * caller's segment order, holds per segment a row of the same layout: segment i's own maximum
+ * and the local time u T_i in [0, T_i] at which it occurs, which shows the segment to lengthen.
+ * The maximum over a trajectory's rows equals its omega_max to the bit.
+ *   On a segment, in u = t / T, E = T^2 f has degree 5 per axis and E' = T^3 p'''.  The leading
+ * terms of E x E' cancel, so its components have degree 8, N = ||E x E'||^2 degree 16 and D =
+ * ||E||^2 degree 10; omega = sqrt(N) / (T D), and its stationary points are the roots of N' D -
+ * 2 N D', of degree 25, which the derivative ladder of the bounds call locates.  The candidates
+ * are the segment ends and the ladder's 25 slots, and every value is evaluated from the axis
+ * polynomials at the candidate (f and p''' by Horner, the cross product, the sums of squares),
+ * never from convolved coefficients.  Where the cross product is exactly 0.0, omega is 0.0
+ * whatever the denominator: a constant trajectory and a purely vertical one give omega_max ==
+ * 0.0 for every g, 0 included.  O(M) work per trajectory, no resolution.
+ *   g (m/s^2) must be finite and >= 0, else TGMS_ERR_INVALID_ARG.
+ *   flags: TGMS_RATE_HIGH when omega_max > omega_limit, a strict comparison on the very value
+ * stored; an infinite omega_limit is unchecked; NaN is TGMS_ERR_INVALID_ARG.  A trajectory with
+ * a non-finite coefficient, time or result, with a T_i that is not > 0 or, in the device call,
+ * with a segment count outside 1..TGMS_MAX_SEGMENTS (nothing is read for it) gets
+ * TGMS_FEAS_NONFINITE alone, an all-NaN record and all-NaN seg_rec rows (for a bad segment count
+ * no row is written either); its neighbours are unaffected.
+ *   Accuracy, with F = f_max and m = f_min of the thrust record and J = j_peak of the bounds
+ * record, when m > 0:
+ *     |omega_max - true| <= 1e-9 F J / m^2
+ * (the rounding of f is relative to F, that of p''' to J; omega <= J / m; the quotient amplifies
+ * by F / m).  Where the thrust vanishes on the trajectory omega is unbounded and there is no
+ * accuracy claim; TGMS_THRUST_LOW of the thrust call is what catches such a trajectory.  fp64
+ * evaluations at located candidates, not a certificate; a touch of a derivative without a sign
+ * change may be skipped, as for the bounds.
+ *   At least one of rec / seg_rec / flags must be non-NULL; fp64 device arrays are 16-byte
+ * aligned; B == 0 is TGMS_OK and launches nothing.  tgms_rate_batch_device is one kernel launch
+ * with no host plan and no handle scratch, so it may be captured into a HIP graph for any batch,
+ * ragged included.  On a multi handle it runs on device 0; on a host handle it returns
+ * TGMS_ERR_UNSUPPORTED.  tgms_rate_batch on a host handle computes on the calling thread (the
+ * same algorithm; host and device agree to the accuracy above, not to the bit); on a GPU handle
+ * it does one upload, the launch and one download, like tgms_thrust_batch. */
+#define TGMS_RATE_STRIDE 2 /* omega_max t_omega */
+#define TGMS_RATE_HIGH 1   /* omega_max > omega_limit */
+/* TGMS_FEAS_NONFINITE (16) is reused */
+tgms_status tgms_rate_batch_device(tgms_handle* h, int32_t B, const int32_t* d_seg_offsets,
+                                   const double* d_seg_times, const double* d_coeffs, double g,
+                                   double omega_limit, double* d_rec /* [B][TGMS_RATE_STRIDE], nullable */,
+                                   double* d_seg_rec /* [S][TGMS_RATE_STRIDE], nullable */,
+                                   int32_t* d_flags /* [B], nullable */, void* stream);
+tgms_status tgms_rate_batch(tgms_handle* h, int32_t B, const int32_t* seg_offsets, const double* seg_times,
+                            const double* coeffs, double g, double omega_limit, double* rec, double* seg_rec,
+                            int32_t* flags);
 
 /* ---- time dilation: the least uniform stretch that meets the dynamic limits ----
  * The step after the check.  tgms_bounds_batch and tgms_thrust_batch flag a candidate; this

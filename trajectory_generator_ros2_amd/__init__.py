@@ -8,6 +8,7 @@ marshals buffers for tests, the benchmark and multi-GPU sharding.
 from ._lib import (DIL_ACCEL, DIL_CAPPED, DIL_EVALS_SHIFT, DIL_FLAG_MASK, DIL_JERK, DIL_NONE, DIL_SPEED, DIL_THRUST_HIGH,
                    DIL_THRUST_LOW, DIL_TILT)
 from ._lib import CUT_DONE, CUT_FINISHED, CUT_SNAPPED
+from ._lib import RATE_HIGH, RATE_STRIDE
 from ._lib import (CLR_BAD_OBSTACLE, COR_BAD_FACE, COR_MAX_FACES, COR_OUTSIDE, COR_STRIDE, ERR_DEVICE, ERR_INVALID_ARG,
                    ERR_NO_DEVICE, ERR_NONFINITE, ERR_SINGULAR, ERR_SKIPPED,
                    ERR_UNSUPPORTED, EXTREMA_STRIDE, FEAS_ACCEL, FEAS_BOX, FEAS_JERK, FEAS_NONFINITE, FEAS_SPEED,
@@ -22,6 +23,7 @@ __all__ = [
     "EXTREMA_STRIDE", "FEAS_BOX", "FEAS_SPEED", "FEAS_ACCEL", "FEAS_JERK", "FEAS_NONFINITE", "Limits",
     "SEP_STRIDE", "SEP_CLOSE", "SEP_NONFINITE", "NEAR_NONE", "CLR_BAD_OBSTACLE", "TgmsError",
     "THRUST_STRIDE", "THRUST_LOW", "THRUST_HIGH", "THRUST_TILT", "ThrustLimits",
+    "RATE_STRIDE", "RATE_HIGH",
     "DIL_CAPPED", "DIL_FLAG_MASK", "DIL_EVALS_SHIFT", "DIL_NONE", "DIL_SPEED", "DIL_ACCEL", "DIL_JERK",
     "DIL_THRUST_HIGH", "DIL_THRUST_LOW", "DIL_TILT",
     "COR_STRIDE", "COR_MAX_FACES", "COR_OUTSIDE", "COR_BAD_FACE",

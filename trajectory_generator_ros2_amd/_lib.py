@@ -26,6 +26,8 @@ NEAR_NONE = -1  # tgms_neighbors_batch: nobody within r_min
 CLR_BAD_OBSTACLE = 32  # tgms_clearance_batch: an unusable obstacle was left out
 THRUST_STRIDE = 6  # f_min t_fmin f_max t_fmax tilt_max t_tilt
 THRUST_LOW, THRUST_HIGH, THRUST_TILT = 1, 2, 4  # with FEAS_NONFINITE
+RATE_STRIDE = 2  # omega_max t_omega
+RATE_HIGH = 1  # with FEAS_NONFINITE
 DIL_CAPPED = 1  # tgms_dilate_batch: still infeasible at s_hi; with FEAS_NONFINITE
 DIL_FLAG_MASK, DIL_EVALS_SHIFT = 0xFF, 8  # flags >> 8: evaluations of the thrust record
 DIL_NONE, DIL_SPEED, DIL_ACCEL, DIL_JERK, DIL_THRUST_HIGH, DIL_THRUST_LOW, DIL_TILT = range(7)  # the active limit
@@ -49,6 +51,7 @@ EXPORTS = [
     "tgms_neighbors_batch", "tgms_neighbors_batch_device",
     "tgms_clearance_batch", "tgms_clearance_batch_device",
     "tgms_thrust_batch", "tgms_thrust_batch_device",
+    "tgms_rate_batch", "tgms_rate_batch_device",
     "tgms_dilate_batch", "tgms_dilate_batch_device",
     "tgms_corridor_batch", "tgms_corridor_batch_device",
     "tgms_corridor_split_batch", "tgms_corridor_split_batch_device",
@@ -194,6 +197,10 @@ def load(path: str = ""):
     L.tgms_thrust_batch_device.restype = ctypes.c_int
     L.tgms_thrust_batch.argtypes = [vp, i32, vp, vp, vp, dbl, ctypes.POINTER(ThrustLimits), vp, vp]
     L.tgms_thrust_batch.restype = ctypes.c_int
+    L.tgms_rate_batch_device.argtypes = [vp, i32, vp, vp, vp, dbl, dbl, vp, vp, vp, vp]
+    L.tgms_rate_batch_device.restype = ctypes.c_int
+    L.tgms_rate_batch.argtypes = [vp, i32, vp, vp, vp, dbl, dbl, vp, vp, vp]
+    L.tgms_rate_batch.restype = ctypes.c_int
     L.tgms_dilate_batch_device.argtypes = [vp, i32, vp, vp, vp, dbl, ctypes.POINTER(Limits),
                                            ctypes.POINTER(ThrustLimits), dbl, dbl, vp, vp, vp, vp, vp, vp]
     L.tgms_dilate_batch_device.restype = ctypes.c_int

@@ -2073,6 +2073,67 @@ tgms_status tgms_thrust_batch(tgms_handle* h, int32_t B, const int32_t* so, cons
     return out.download(h);
 }
 
+// ---- continuous body-rate bound: peak roll/pitch rate from differential flatness ----
+
+// The argument rules the two rate entry points share (include/tgms.h); *limit is what a launch
+// carries: an infinite omega_limit of either sign is unchecked.
+static tgms_status check_rate(tgms_handle* h, int32_t B, double g, double omega_limit, bool any_output,
+                              double* limit) {
+    if (B < 0 || !(g >= 0.0) || !std::isfinite(g)) return set_err(h, TGMS_ERR_INVALID_ARG, "bad B or g");
+    if (std::isnan(omega_limit)) return set_err(h, TGMS_ERR_INVALID_ARG, "NaN limit");
+    *limit = std::isfinite(omega_limit) ? omega_limit : std::numeric_limits<double>::infinity();
+    if (!any_output) return set_err(h, TGMS_ERR_INVALID_ARG, "every output is NULL");
+    return TGMS_OK;
+}
+
+tgms_status tgms_rate_batch_device(tgms_handle* h, int32_t B, const int32_t* d_so, const double* dT,
+                                   const double* dC, double g, double omega_limit, double* d_rec,
+                                   double* d_seg_rec, int32_t* d_flags, void* stream) {
+    if (tgms_status e = enter(h, __func__); e != TGMS_OK) return e;
+    double lim;
+    const tgms_status s = check_rate(h, B, g, omega_limit, d_rec || d_seg_rec || d_flags, &lim);
+    if (s != TGMS_OK) return s;
+    if (B == 0) return TGMS_OK;
+    if (!d_so || !dT || !dC) return set_err(h, TGMS_ERR_INVALID_ARG, "NULL device pointer");
+    TGMS_CHECK_ALIGNED(h, dT, dC, d_rec, d_seg_rec);
+    TGMS_HIP(h, tgms::launch_rate(B, d_so, dT, dC, g, lim, d_rec, d_seg_rec, d_flags, static_cast<hipStream_t>(stream)));
+    return TGMS_OK;
+}
+
+tgms_status tgms_rate_batch(tgms_handle* h, int32_t B, const int32_t* so, const double* seg_times,
+                            const double* coeffs, double g, double omega_limit, double* rec, double* seg_rec,
+                            int32_t* flags) {
+    if (tgms_status e = enter(h); e != TGMS_OK) return e;
+    tgms_status s = check_offsets(h, B, so, TGMS_MAX_SEGMENTS, nullptr, nullptr);
+    if (s != TGMS_OK) return s;
+    double lim;
+    s = check_rate(h, B, g, omega_limit, rec || seg_rec || flags, &lim);
+    if (s != TGMS_OK) return s;
+    if (B == 0) return TGMS_OK;
+    if (!seg_times || !coeffs) return set_err(h, TGMS_ERR_INVALID_ARG, "NULL pointer");
+    if (h->host) {
+        for (int32_t b = 0; b < B; ++b) {
+            const int64_t s0 = so[b];
+            const int fl = tgms::host::rate(so[b + 1] - so[b], coeffs + s0 * 24, seg_times + s0, g, lim,
+                                            rec ? rec + (int64_t)b * TGMS_RATE_STRIDE : nullptr,
+                                            seg_rec ? seg_rec + s0 * TGMS_RATE_STRIDE : nullptr);
+            if (flags) flags[b] = fl;
+        }
+        return TGMS_OK;
+    }
+    const size_t S = (size_t)so[B];
+    double *dT, *dC;
+    int32_t* dSo;
+    Outputs out;
+    const auto oSeg = out.add(seg_rec, S * TGMS_RATE_STRIDE);
+    const auto oRec = out.add(rec, (size_t)B * TGMS_RATE_STRIDE);
+    const auto oFl = out.add(flags, (size_t)B);
+    s = stage(h, {input(&dT, seg_times, S), input(&dC, coeffs, S * 24), input(&dSo, so, (size_t)B + 1), output(&out)});
+    if (s != TGMS_OK) return s;
+    TGMS_HIP(h, tgms::launch_rate(B, dSo, dT, dC, g, lim, out.dev(oRec), out.dev(oSeg), out.dev(oFl), h->stream));
+    return out.download(h);
+}
+
 // ---- time dilation: the least uniform stretch that meets the dynamic limits ----
 
 // The argument rules the two dilation entry points share (include/tgms.h), and the six limits a

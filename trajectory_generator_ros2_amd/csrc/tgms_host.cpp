@@ -33,6 +33,7 @@
 #include "tgms_dilate_core.h"
 #include "tgms_neighbors_core.h"
 #include "tgms_separation_core.h"
+#include "tgms_rate_core.h"
 #include "tgms_thrust_core.h"
 
 namespace tgms {
@@ -365,6 +366,36 @@ int thrust(int M, const double* C, const double* T, double g, const tgms_thrust_
     double r[TGMS_THRUST_STRIDE];
     const int fl = th::finish(f, bad, lim ? *lim : none, r);
     for (int q = 0; q < TGMS_THRUST_STRIDE; ++q) rec[q] = r[q];
+    return fl;
+}
+
+int rate(int M, const double* C, const double* T, double g, double omega_limit, double* rec, double* seg_rec) {
+    namespace rt = tgms::rate;
+    const bool count_ok = M >= 1 && M <= TGMS_MAX_SEGMENTS;
+    double chk = 0.0;
+    bool bad = !count_ok;
+    for (int i = 0; !bad && i < M; ++i) {
+        chk += T[i] * 0.0;
+        bad = bad || !(T[i] > 0.0);
+    }
+    for (int q = 0; !bad && q < M * 24; ++q) chk += C[q] * 0.0;
+    bad = bad || !finite(chk);
+    rt::Item items[TGMS_MAX_SEGMENTS];
+    rt::Fold f = rt::fold_init();
+    for (int i = 0; !bad && i < M; ++i) {  // tgms_rate_core.h: the kernel's items, one after the other
+        rt::rate_item(C + i * 24, T[i], g, items[i]);
+        rt::fold(f, items[i], T[i]);
+    }
+    double r[TGMS_RATE_STRIDE];
+    const int fl = rt::finish(f, bad, omega_limit, r);
+    if (rec)
+        for (int q = 0; q < TGMS_RATE_STRIDE; ++q) rec[q] = r[q];
+    for (int i = 0; seg_rec && count_ok && i < M; ++i) {
+        const rt::Item none{0.0, 0.0};
+        const bool nan = (fl & TGMS_FEAS_NONFINITE) != 0;
+        rt::seg_row(nan ? none : items[i], nan ? 0.0 : T[i], nan, seg_rec[i * TGMS_RATE_STRIDE],
+                    seg_rec[i * TGMS_RATE_STRIDE + 1]);
+    }
     return fl;
 }
 

@@ -40,6 +40,15 @@ int bounds(int M, const double* coeffs, const double* seg_times, const tgms_limi
 int thrust(int M, const double* coeffs, const double* seg_times, double g, const tgms_thrust_limits* lim,
            double* rec);
 
+// The continuous body-rate bound (include/tgms.h tgms_rate_batch) of one trajectory: rec
+// [TGMS_RATE_STRIDE] = omega_max t_omega of ||f x p'''|| / ||f||^2, seg_rec [M][TGMS_RATE_STRIDE]
+// each segment's own maximum and local time (either nullable); returns TGMS_RATE_HIGH against
+// omega_limit (+inf: unchecked), TGMS_FEAS_NONFINITE alone (rec and, for a usable segment count,
+// the M rows all NaN) for an unusable trajectory.  The algorithm is the kernel's
+// (tgms_rate_core.h), one segment after the other.
+int rate(int M, const double* coeffs, const double* seg_times, double g, double omega_limit, double* rec,
+         double* seg_rec);
+
 // Time dilation (include/tgms.h tgms_dilate_batch) of one trajectory: the least stretch in
 // [s_lo, s_hi] that meets lim (tgms_dilate_core.h, resolved) into *scale, the TGMS_DIL_* code of
 // the active limit into *active, the scaled times into T_out [M] and coefficients into C_out

@@ -145,6 +145,12 @@ hipError_t launch_bounds(int32_t B, const int32_t* seg_offsets, const double* T,
 hipError_t launch_thrust(int32_t B, const int32_t* seg_offsets, const double* T, const double* C, double g,
                          const tgms_thrust_limits& lim, double* rec, int32_t* flags, hipStream_t stream);
 
+// Continuous body-rate bound (tgms_rate.hip): per trajectory omega_max t_omega of ||f x p'''|| /
+// ||f||^2 into rec [B][TGMS_RATE_STRIDE], per segment its own maximum and local time into seg_rec
+// [S][TGMS_RATE_STRIDE] and flags [B] (each nullable); the mapping of launch_thrust, one launch.
+hipError_t launch_rate(int32_t B, const int32_t* seg_offsets, const double* T, const double* C, double g,
+                       double omega_limit, double* rec, double* seg_rec, int32_t* flags, hipStream_t stream);
+
 // Time dilation (tgms_dilate.hip): per trajectory the least stretch s in [s_lo, s_hi] that meets
 // lim (tgms_dilate_core.h: the six limits, resolved) into scale [B], the active limit into active
 // [B], flags [B], the scaled times into T_out [S] and coefficients into C_out [S][3][8] (each

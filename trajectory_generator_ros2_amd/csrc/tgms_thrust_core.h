@@ -45,9 +45,9 @@
 //   - Where thrust vanishes, theta jumps (by pi on a vertical trajectory): the stored tilt is
 //     the maximum over the candidates and carries no accuracy claim there; f_min says so.
 //   - Not a certificate, and a touch without a sign change may be skipped, as for the bounds.
-// Body rate |f x p'''| / ||f||^2 is not computed: its stationary points are roots of a
-// polynomial of degree 27, twice the ladder depth the register budget carries.  j_peak / f_min
-// from the bounds and thrust records is a sound upper bound.
+// Body rate |f x p'''| / ||f||^2 is tgms_rate_core.h's: its stationary points are the roots of
+// a polynomial of degree 25, a ladder of its own at one wave per SIMD.  j_peak / f_min from the
+// bounds and thrust records is a sound but loose upper bound of it.
 #pragma once
 
 #include "tgms_bounds_core.h"

@@ -189,6 +189,25 @@ class Solver:
             raise TgmsError(st, self.last_error())
         return rec, flags
 
+    def rate(self, seg_offsets, seg_times, coeffs, g: float = 9.80665,
+             omega_limit: float = float("inf")) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+        """Continuous body-rate bound (include/tgms.h tgms_rate_batch): (rec [B,2] = omega_max
+        t_omega of the roll/pitch rate ||f x p'''|| / ||f||^2 with f = p'' + g e_z, seg_rec [S,2]
+        = each segment's own maximum and local time, flags [B]: RATE_HIGH against `omega_limit`;
+        inf checks nothing)."""
+        so = np.ascontiguousarray(seg_offsets, dtype=np.int32)
+        T = np.ascontiguousarray(seg_times, dtype=np.float64).reshape(-1)
+        C = np.ascontiguousarray(coeffs, dtype=np.float64)
+        B = so.shape[0] - 1
+        rec = np.zeros((B, _lib.RATE_STRIDE), dtype=np.float64)
+        seg_rec = np.zeros((T.shape[0], _lib.RATE_STRIDE), dtype=np.float64)
+        flags = np.zeros(B, dtype=np.int32)
+        st = self._L.tgms_rate_batch(self._h, B, _ptr(so), _ptr(T), _ptr(C), float(g), float(omega_limit),
+                                     _ptr(rec), _ptr(seg_rec), _ptr(flags))
+        if st != _lib.OK:
+            raise TgmsError(st, self.last_error())
+        return rec, seg_rec, flags
+
     def dilate(self, seg_offsets, seg_times, coeffs, g: float = 9.80665, limits: Optional[_lib.Limits] = None,
                tlimits: Optional[_lib.ThrustLimits] = None, s_lo: float = 1.0, s_hi: float = 100.0):
         """Time dilation (include/tgms.h tgms_dilate_batch): per trajectory the least stretch s in
@@ -512,6 +531,17 @@ class Solver:
                                               _ptr(d_coeffs), float(g),
                                               None if limits is None else ctypes.byref(limits),
                                               _ptr(d_rec), _ptr(d_flags), ctypes.c_void_p(stream))
+        if st != _lib.OK:
+            raise TgmsError(st, self.last_error())
+
+    def rate_device(self, B: int, d_seg_offsets, d_seg_times, d_coeffs, g: float = 9.80665,
+                    omega_limit: float = float("inf"), d_rec=None, d_seg_rec=None, d_flags=None,
+                    stream: int = 0) -> None:
+        """tgms_rate_batch_device: d_rec [B,2] fp64, d_seg_rec [S,2] fp64 and / or d_flags [B]
+        int32 (at least one); g and `omega_limit` travel as kernel arguments."""
+        st = self._L.tgms_rate_batch_device(self._h, int(B), _ptr(d_seg_offsets), _ptr(d_seg_times),
+                                            _ptr(d_coeffs), float(g), float(omega_limit), _ptr(d_rec),
+                                            _ptr(d_seg_rec), _ptr(d_flags), ctypes.c_void_p(stream))
         if st != _lib.OK:
             raise TgmsError(st, self.last_error())
 
