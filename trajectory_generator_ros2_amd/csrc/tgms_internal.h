@@ -92,7 +92,7 @@ hipError_t launch_group_perm(int32_t B, const int32_t* seg_offsets, const int32_
 // the per-M totals summed from k_perm_hist's block counts, the starts of the M groups in
 // the permutation and both occupancy classes' group tables.  The host plans nothing per
 // trajectory, and a captured graph stays valid for any offsets of the same B and S: each
-// replay regroups.  `so` may be a slice of a larger batch's offsets (so[0] != 0: the
+// replay regroups (held by tests/test_gpu_refine_plan.py).  `so` may be a slice of a larger batch's offsets (so[0] != 0: the
 // kernels subtract so_base = so[0]); offsets whose M leave 1..16 or whose span is not S
 // mark the plan bad and nothing runs: statuses TGMS_ERR_INVALID_ARG, the S segments'
 // coefficients (C, nullable) and the n costs (cost, nullable) exact zeros, times kept.

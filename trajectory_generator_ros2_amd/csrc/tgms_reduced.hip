@@ -612,6 +612,7 @@ template <class O>
 struct CostOutT {
     O o;
     mutable double J;
+    bool store;  // false (uniform): a loop called with d_coeffs = NULL keeps the cost and stores nothing
 };
 using CostOut = CostOutT<OutCtx>;
 template <class T>
@@ -723,7 +724,7 @@ __device__ __forceinline__ void emit_axis_v(const Out& o, double ws, double we, 
             const bool mine = has_r || !right;  // as for GradAcc
             o.J += mine ? r * seg_cost_q(P4, P5, P6, P7) : 0.0;
             asm volatile("" : "+v"(o.J));
-            emit_c<M>(o.o, c, a, e, has_r);
+            if (o.store) emit_c<M>(o.o, c, a, e, has_r);
         } else {
             emit_c<M>(o, c, a, e, has_r);
         }
@@ -1696,26 +1697,19 @@ __device__ __forceinline__ void refine_loop_block(Stage<M>& sm, int64_t blk, int
     __syncthreads();
     const bool valid = sm.in.bad[slot] == 0;
     const double* ed = (HAS_ED && live) ? ED + (int64_t)b * 18 : ED;
-    int32_t st_last = TGMS_OK;
-    for (int32_t it = 0; it <= iters; ++it) {  // it == iters: the cost at the final times
+    for (int32_t it = 0; it < iters; ++it) {  // the last pass (the cost at the final times) follows the loop
         const LaneView L = make_view<M>(sm.in, slot, right);
-        if (C && it == iters) break;  // the last pass follows the loop
         GradAcc<NE> G;
         G.J = 0.0;
 #pragma unroll
         for (int e = 0; e < NE; ++e) G.dJ[e] = 0.0;
         const int32_t st = pair_solve<M, HAS_ED, GradAcc<NE>>(L, right, valid, ed, G);
-        st_last = st;
         double Fl = live ? G.J : 0.0;
 #pragma unroll
         for (int e = 0; e < NE; ++e) {
             if (live && e < nmine) Fl += kT * Tl[e];
         }
         const double F = Fl + pair_swap(Fl);
-        if (it == iters) {
-            if (live && !right && cost) cost[b] = F;
-            break;
-        }
         const bool ok = (st == TGMS_OK) && F > 0.0;
         const double iF = 1.0 / F;  // one division per lane and step, not one per segment (round 6)
         __syncthreads();  // every lane has read the stage before the times change
@@ -1733,35 +1727,29 @@ __device__ __forceinline__ void refine_loop_block(Stage<M>& sm, int64_t blk, int
         }
         __syncthreads();
     }
-    if (C) {
-        const LaneView L = make_view<M>(sm.in, slot, right);
-        // the last pass: the coefficients at the final times and the cost there from
-        // one solve (a separate cost pass and emission pass before: 12 -> 11 solves
-        // per trajectory at 10 steps)
-#pragma unroll
-        for (int e = 0; e < NE; ++e) {
-            if (live && valid && e < nmine) T[s0 + (right ? M - 1 - e : e)] = Tl[e];
-        }
-        // kT sum T first: the times are dead during the solve
-        double Ft = 0.0;
-#pragma unroll
-        for (int e = 0; e < NE; ++e) {
-            if (live && e < nmine) Ft += kT * Tl[e];
-        }
-        const CostOut O{make_out(sm.O, sm.in.base, C, nb, lane), 0.0};
-        const int32_t st = pair_solve<M, HAS_ED, CostOut>(L, right, valid, ed, O);
-        const double Fl = live ? O.J + Ft : 0.0;
-        const double F = Fl + pair_swap(Fl);
-        if (live && !right && cost) cost[b] = F;
-        if (live && st == TGMS_ERR_NONFINITE) zero_traj(C + sm.in.base[slot], M * 24, right, 2);
-        if (live && !right && status) status[b] = st;
-        return;
-    }
+    const LaneView L = make_view<M>(sm.in, slot, right);
+    // the last pass: the coefficients at the final times and the cost there from
+    // one solve (a separate cost pass and emission pass before: 12 -> 11 solves
+    // per trajectory at 10 steps)
 #pragma unroll
     for (int e = 0; e < NE; ++e) {
         if (live && valid && e < nmine) T[s0 + (right ? M - 1 - e : e)] = Tl[e];
     }
-    if (live && !right && status) status[b] = st_last;
+    // kT sum T first: the times are dead during the solve
+    double Ft = 0.0;
+#pragma unroll
+    for (int e = 0; e < NE; ++e) {
+        if (live && e < nmine) Ft += kT * Tl[e];
+    }
+    // without coefficients (C == NULL) the same pass stores nothing, so the cost is the same
+    // number, bit for bit, whether or not the caller asked for the coefficients
+    const CostOut O{make_out(sm.O, sm.in.base, C, nb, lane), 0.0, C != nullptr};
+    const int32_t st = pair_solve<M, HAS_ED, CostOut>(L, right, valid, ed, O);
+    const double Fl = live ? O.J + Ft : 0.0;
+    const double F = Fl + pair_swap(Fl);
+    if (live && !right && cost) cost[b] = F;
+    if (C && live && st == TGMS_ERR_NONFINITE) zero_traj(C + sm.in.base[slot], M * 24, right, 2);
+    if (live && !right && status) status[b] = st;
 }
 
 template <int M, bool HAS_ED>
