@@ -40,7 +40,8 @@
  *     handle must be replayed in stream order with each other.  Calls that upload a
  *     host-side launch plan or grow scratch at call time (ragged batches,
  *     tgms_refine_loop_device, tgms_neighbors_batch_device, tgms_clearance_batch_device,
- *     tgms_corridor_split_batch_device, tgms_cut_batch_device, the multi-GPU calls, a band
+ *     tgms_corridor_split_batch_device, tgms_cut_batch_device,
+ *     tgms_field_clearance_batch_device with lip == 0, the multi-GPU calls, a band
  *     capture with no slab large enough) return TGMS_ERR_UNSUPPORTED while their stream is
  *     capturing.
  *     tgms_extrema_batch_device, tgms_bounds_batch_device, tgms_thrust_batch_device,
@@ -116,7 +117,7 @@ tgms_status tgms_create(tgms_handle** out, int device);
 /* The explicit host backend (BASELINE config 1: a ROS 2 node with no GPU; the reference
  * generates on the executor thread's CPU, src/TrajectoryGenerator.cpp:54-57, :71).  A host
  * handle runs tgms_solve_batch (reduced method), tgms_sample_batch, tgms_extrema_batch,
- * tgms_bounds_batch, tgms_thrust_batch, tgms_rate_batch, tgms_dilate_batch, tgms_corridor_batch, tgms_corridor_split_batch, tgms_cut_batch, tgms_separation_batch, tgms_neighbors_batch and tgms_clearance_batch on the calling thread with the GPU path's conventions; every other entry point returns
+ * tgms_bounds_batch, tgms_thrust_batch, tgms_rate_batch, tgms_dilate_batch, tgms_corridor_batch, tgms_corridor_split_batch, tgms_cut_batch, tgms_separation_batch, tgms_neighbors_batch, tgms_clearance_batch and tgms_field_clearance_batch on the calling thread with the GPU path's conventions; every other entry point returns
  * TGMS_ERR_UNSUPPORTED on it.  Chosen by the caller only: tgms_create never falls back to
  * it. */
 tgms_status tgms_create_host(tgms_handle** out);
@@ -476,6 +477,78 @@ tgms_status tgms_clearance_batch(tgms_handle* h, int32_t B, const int32_t* seg_o
                                  const double* coeffs, int32_t K, const double* obstacles, const double* scale,
                                  double r_min, double* near, int32_t* obs, int32_t* count, int32_t* tested,
                                  int32_t* flags);
+
+/* ---- distance-field clearance: certified closest approach to a voxel map ----
+ * The same question for a planner whose world is a map: a Euclidean signed distance field on a
+ * voxel grid.  The cost of the call does not depend on how many obstacles the map holds.
+ *   The field.  `field` (a host struct) describes the grid, `values` holds one fp32 node per
+ * grid point, x fastest.  With q_a = clamp((p_a - origin_a) / h, 0, n_a - 1), i_a = min(floor
+ * q_a, n_a - 2) and f_a = q_a - i_a, phi(p) is the trilinear interpolation of the eight nodes
+ * of cell i at f, the nodes converted to fp64 and blended in fp64.  Outside the grid phi is
+ * the value at the clamped point; there is no "left the map" flag, because tgms_bounds_batch
+ * with pmin / pmax set to the grid's extent answers that exactly.  phi is Lipschitz with
+ *     L = sqrt(G_x^2 + G_y^2 + G_z^2),  G_a = max over edges along a of |v(node + e_a) - v(node)| / h
+ * (the derivative along a is a bilinear blend of edge differences; clamping is 1-Lipschitz);
+ * for a true distance field L <= sqrt(3).
+ *   lip > 0 is taken as L.  A value below the true L voids the certificate; that is the
+ * caller's to get right.  lip == 0 makes the call reduce L from the values on the device, in
+ * launches of its own before the search; the result stays on the device.
+ *   Per trajectory b, with D_b the prefix sum of its times as in the clearance call and m* the
+ * minimum of phi(p(t)) over [0, D_b]:
+ *     near[b]    d_min t_min: t_min in [0, D_b] is a knot's prefix sum plus the local time,
+ *                clamped, and d_min the value the call evaluated there
+ *     evals[b]   the evaluations of phi the row took; every knot (the left end of every
+ *                segment, the right end of the last) is always evaluated, so evals >= M + 1
+ *     flags[b]   TGMS_SEP_CLOSE when d_min < r_min (strict, on the stored value);
+ *                TGMS_FLD_UNRESOLVED when the row would have needed more than max_evals
+ *                evaluations: it stops there and only (1) holds
+ *   (1) Upper bound: d_min = phi(p(t_min)), so d_min >= m*.
+ *   (2) Certificate, without TGMS_FLD_UNRESOLVED: m* >= min(d_min - tol, r_min).  So d_min is
+ * within tol of the true minimum whenever d_min - tol < r_min, and a row without TGMS_SEP_CLOSE
+ * stays at least r_min - tol away.  r_min = +inf resolves every row to tol.
+ *   The search is a branch-and-bound over each segment's interval tree.  An interval is
+ * discarded only when phi at its centre less L times the distance the vehicle can cover in
+ * half the interval is at least min(best - tol, r_min), best the least value evaluated so far
+ * for the trajectory; the distance comes from bounds of the speed and the acceleration on the
+ * segment (Bernstein control values) and the speed at the centre.  The cost follows how close
+ * the trajectory comes, not its duration over a step.  Both guarantees hold up to
+ * 1e-9 (F + L (P + h)), F the largest |value| and P the largest coordinate magnitude the
+ * trajectory reaches.  No result depends on the launch shape.
+ *   An unusable row (in the device call a segment count outside 1..TGMS_MAX_SEGMENTS, for which
+ * nothing is read; a time that is not finite and > 0; a non-finite coefficient; a non-finite
+ * evaluated value) gets TGMS_SEP_NONFINITE alone, near = NaN NaN and evals = 0.  The values are
+ * the caller's to keep finite; which rows meet a non-finite node is unspecified.
+ *   TGMS_ERR_INVALID_ARG: an n_a < 2; n_x n_y n_z > 2^31 - 1; h or an origin component not
+ * finite; h <= 0; tol not finite or not > 0; r_min NaN or <= 0 (+inf is legal); lip negative
+ * or not finite; max_evals < 1; field or values NULL; near, evals and flags all NULL; in the
+ * device call a d_seg_times, d_coeffs or d_near that is not 16-byte aligned or d_values not
+ * 4-byte aligned.  B == 0 is TGMS_OK and launches nothing.
+ *   With lip > 0 the device call is one launch, uses no handle scratch and may be captured
+ * into a HIP graph.  With lip == 0 it needs handle scratch for the reduction, ordered like all
+ * handle scratch, so it returns TGMS_ERR_UNSUPPORTED while its stream is capturing.  On a
+ * multi handle it runs on device 0; on a host handle the device call returns
+ * TGMS_ERR_UNSUPPORTED and the host-pointer call computes on the calling thread from the same
+ * core (host and device agree within the guarantees, not to the bit: they visit the intervals
+ * in different orders).  On a GPU handle the host-pointer call uploads the values with the
+ * batch every time; a caller with a large map should keep it on the device and use the device
+ * call. */
+typedef struct tgms_field {
+    double origin[3]; /* position of node (0,0,0) */
+    double h;         /* node spacing, the same on all axes */
+    int32_t n[3];     /* nodes per axis; values[(k*n[1] + j)*n[0] + i], x fastest */
+} tgms_field;
+#define TGMS_FLD_UNRESOLVED 64 /* the row spent max_evals; only the upper bound holds */
+tgms_status tgms_field_clearance_batch_device(tgms_handle* h, int32_t B, const int32_t* d_seg_offsets,
+                                              const double* d_seg_times, const double* d_coeffs,
+                                              const tgms_field* field /* host */, const float* d_values, double lip,
+                                              double r_min, double tol, int32_t max_evals,
+                                              double* d_near /* [B][TGMS_SEP_STRIDE]: d_min t_min, nullable */,
+                                              int32_t* d_evals /* [B], nullable */,
+                                              int32_t* d_flags /* [B], nullable */, void* stream);
+tgms_status tgms_field_clearance_batch(tgms_handle* h, int32_t B, const int32_t* seg_offsets, const double* seg_times,
+                                       const double* coeffs, const tgms_field* field, const float* values, double lip,
+                                       double r_min, double tol, int32_t max_evals, double* near, int32_t* evals,
+                                       int32_t* flags);
 
 /* ---- continuous thrust and tilt bounds from differential flatness ----
  * Which candidates the vehicle can fly.  The dynamic limits of tgms_limits bound |p''|, but

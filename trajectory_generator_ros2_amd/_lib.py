@@ -24,6 +24,7 @@ SEP_STRIDE = 2  # d_min t_min
 SEP_CLOSE, SEP_NONFINITE = 1, 16
 NEAR_NONE = -1  # tgms_neighbors_batch: nobody within r_min
 CLR_BAD_OBSTACLE = 32  # tgms_clearance_batch: an unusable obstacle was left out
+FLD_UNRESOLVED = 64  # tgms_field_clearance_batch: the row spent max_evals; only the upper bound holds
 THRUST_STRIDE = 6  # f_min t_fmin f_max t_fmax tilt_max t_tilt
 THRUST_LOW, THRUST_HIGH, THRUST_TILT = 1, 2, 4  # with FEAS_NONFINITE
 RATE_STRIDE = 2  # omega_max t_omega
@@ -50,6 +51,7 @@ EXPORTS = [
     "tgms_separation_batch", "tgms_separation_batch_device",
     "tgms_neighbors_batch", "tgms_neighbors_batch_device",
     "tgms_clearance_batch", "tgms_clearance_batch_device",
+    "tgms_field_clearance_batch", "tgms_field_clearance_batch_device",
     "tgms_thrust_batch", "tgms_thrust_batch_device",
     "tgms_rate_batch", "tgms_rate_batch_device",
     "tgms_dilate_batch", "tgms_dilate_batch_device",
@@ -95,6 +97,18 @@ class ThrustLimits(ctypes.Structure):
     def __init__(self, f_min=float("-inf"), f_max=float("inf"), tilt_max=float("inf")):
         super().__init__()
         self.f_min, self.f_max, self.tilt_max = float(f_min), float(f_max), float(tilt_max)
+
+
+class Field(ctypes.Structure):
+    """tgms_field (include/tgms.h): the grid of a distance field: the position of node (0,0,0), the
+    node spacing and the nodes per axis (x fastest in the values)."""
+    _fields_ = [("origin", ctypes.c_double * 3), ("h", ctypes.c_double), ("n", ctypes.c_int32 * 3)]
+
+    def __init__(self, origin=(0.0, 0.0, 0.0), h=1.0, n=(2, 2, 2)):
+        super().__init__()
+        self.origin[:] = [float(x) for x in origin]
+        self.h = float(h)
+        self.n[:] = [int(x) for x in n]
 
 
 _lib = None
@@ -193,6 +207,12 @@ def load(path: str = ""):
     L.tgms_clearance_batch_device.restype = ctypes.c_int
     L.tgms_clearance_batch.argtypes = [vp, i32, vp, vp, vp, i32, vp, vp, dbl, vp, vp, vp, vp, vp]
     L.tgms_clearance_batch.restype = ctypes.c_int
+    L.tgms_field_clearance_batch_device.argtypes = [vp, i32, vp, vp, vp, ctypes.POINTER(Field), vp, dbl, dbl, dbl, i32,
+                                                    vp, vp, vp, vp]
+    L.tgms_field_clearance_batch_device.restype = ctypes.c_int
+    L.tgms_field_clearance_batch.argtypes = [vp, i32, vp, vp, vp, ctypes.POINTER(Field), vp, dbl, dbl, dbl, i32,
+                                             vp, vp, vp]
+    L.tgms_field_clearance_batch.restype = ctypes.c_int
     L.tgms_thrust_batch_device.argtypes = [vp, i32, vp, vp, vp, dbl, ctypes.POINTER(ThrustLimits), vp, vp, vp]
     L.tgms_thrust_batch_device.restype = ctypes.c_int
     L.tgms_thrust_batch.argtypes = [vp, i32, vp, vp, vp, dbl, ctypes.POINTER(ThrustLimits), vp, vp]

@@ -2700,6 +2700,97 @@ tgms_status tgms_clearance_batch(tgms_handle* h, int32_t B, const int32_t* so, c
     return s != TGMS_OK ? s : out.download(h);
 }
 
+// ---- distance-field clearance: certified closest approach to a voxel map ----
+
+// What both calls check before they look at a pointer to the batch.
+static tgms_status check_field(tgms_handle* h, int32_t B, const tgms_field* field, const void* values, double lip,
+                               double r_min, double tol, int32_t max_evals, const void* near, const void* evals,
+                               const void* flags) {
+    if (B < 0) return set_err(h, TGMS_ERR_INVALID_ARG, "bad B");
+    if (!field || !values) return set_err(h, TGMS_ERR_INVALID_ARG, "field or values NULL");
+    int64_t total = 1;
+    for (int a = 0; a < 3; ++a) {
+        if (field->n[a] < 2) return set_err(h, TGMS_ERR_INVALID_ARG, "a field needs at least 2 nodes per axis");
+        if (!std::isfinite(field->origin[a])) return set_err(h, TGMS_ERR_INVALID_ARG, "field origin must be finite");
+        total *= field->n[a];  // < 2^62 after two factors, checked before the third
+        if (total > INT32_MAX) return set_err(h, TGMS_ERR_INVALID_ARG, "a field holds at most 2^31 - 1 nodes");
+    }
+    if (!(field->h > 0.0) || !std::isfinite(field->h)) return set_err(h, TGMS_ERR_INVALID_ARG, "h must be finite and > 0");
+    if (!(tol > 0.0) || !std::isfinite(tol)) return set_err(h, TGMS_ERR_INVALID_ARG, "tol must be finite and > 0");
+    if (!(r_min > 0.0)) return set_err(h, TGMS_ERR_INVALID_ARG, "r_min must be > 0 (+inf allowed)");
+    if (!(lip >= 0.0) || !std::isfinite(lip)) return set_err(h, TGMS_ERR_INVALID_ARG, "lip must be finite and >= 0");
+    if (max_evals < 1) return set_err(h, TGMS_ERR_INVALID_ARG, "max_evals must be >= 1");
+    if (!near && !evals && !flags) return set_err(h, TGMS_ERR_INVALID_ARG, "near, evals and flags all NULL");
+    return TGMS_OK;
+}
+
+// The launches of either call: one with a given bound; with lip == 0 the reduction first, on
+// the handle's scratch.
+static tgms_status run_field(tgms_handle* h, hipStream_t st, int32_t B, const int32_t* d_so, const double* dT,
+                             const double* dC, const tgms_field& field, const float* d_values, double lip, double r_min,
+                             double tol, int32_t max_evals, double* d_near, int32_t* d_evals, int32_t* d_flags) {
+    if (lip > 0.0) {
+        TGMS_HIP(h, hipSetDevice(h->device));
+        TGMS_HIP(h, tgms::launch_field(B, d_so, dT, dC, field, d_values, lip, r_min, tol, max_evals, nullptr, d_near,
+                                       d_evals, d_flags, st));
+        return TGMS_OK;
+    }
+    return launch_on_scratch(h, st, "tgms_field_clearance_batch_device with lip == 0", "launch_field",
+                             tgms::field_scratch_bytes(), [&](void* ws) {
+                                 return tgms::launch_field(B, d_so, dT, dC, field, d_values, lip, r_min, tol, max_evals, ws,
+                                                           d_near, d_evals, d_flags, st);
+                             });
+}
+
+tgms_status tgms_field_clearance_batch_device(tgms_handle* h, int32_t B, const int32_t* d_so, const double* dT,
+                                              const double* dC, const tgms_field* field, const float* d_values,
+                                              double lip, double r_min, double tol, int32_t max_evals, double* d_near,
+                                              int32_t* d_evals, int32_t* d_flags, void* stream) {
+    if (tgms_status e = enter(h, __func__); e != TGMS_OK) return e;
+    const tgms_status s = check_field(h, B, field, d_values, lip, r_min, tol, max_evals, d_near, d_evals, d_flags);
+    if (s != TGMS_OK) return s;
+    if (B == 0) return TGMS_OK;
+    if (!d_so || !dT || !dC) return set_err(h, TGMS_ERR_INVALID_ARG, "NULL device pointer");
+    TGMS_CHECK_ALIGNED(h, dT, dC, d_near);
+    if (reinterpret_cast<uintptr_t>(d_values) & 3u)
+        return set_err(h, TGMS_ERR_INVALID_ARG, "fp32 device buffers must be 4-byte aligned");
+    return run_field(h, static_cast<hipStream_t>(stream), B, d_so, dT, dC, *field, d_values, lip, r_min, tol, max_evals,
+                     d_near, d_evals, d_flags);
+}
+
+tgms_status tgms_field_clearance_batch(tgms_handle* h, int32_t B, const int32_t* so, const double* seg_times,
+                                       const double* coeffs, const tgms_field* field, const float* values, double lip,
+                                       double r_min, double tol, int32_t max_evals, double* near, int32_t* evals,
+                                       int32_t* flags) {
+    if (tgms_status e = enter(h); e != TGMS_OK) return e;
+    tgms_status s = check_offsets(h, B, so, TGMS_MAX_SEGMENTS, nullptr, nullptr);
+    if (s != TGMS_OK) return s;
+    s = check_field(h, B, field, values, lip, r_min, tol, max_evals, near, evals, flags);
+    if (s != TGMS_OK) return s;
+    if (B == 0) return TGMS_OK;
+    if (!seg_times || !coeffs) return set_err(h, TGMS_ERR_INVALID_ARG, "NULL pointer");
+    if (h->host) {
+        tgms::host::field_clearance(B, so, seg_times, coeffs, *field, values, lip, r_min, tol, max_evals, near, evals,
+                                    flags);
+        return TGMS_OK;
+    }
+    // the kernel gets every array; what the caller omitted is dropped on the host
+    const size_t S = (size_t)so[B], n = (size_t)B;
+    const size_t N = (size_t)field->n[0] * field->n[1] * field->n[2];
+    Outputs out;
+    const auto oNear = out.add(near, n * TGMS_SEP_STRIDE, true);
+    const auto oEv = out.add(evals, n, true), oFl = out.add(flags, n, true);
+    double *dT, *dC;
+    float* dV;
+    int32_t* dSo;
+    s = stage(h, {input(&dT, seg_times, S), input(&dC, coeffs, S * 24), input(&dV, values, N), input(&dSo, so, n + 1),
+                  output(&out)});
+    if (s != TGMS_OK) return s;
+    s = run_field(h, h->stream, B, dSo, dT, dC, *field, dV, lip, r_min, tol, max_evals, out.dev(oNear), out.dev(oEv),
+                  out.dev(oFl));
+    return s != TGMS_OK ? s : out.download(h);
+}
+
 // ---- multi-GPU ----
 
 tgms_status tgms_create_multi(tgms_handle** out, int device_count) {

@@ -31,6 +31,7 @@
 #include "tgms_corridor_split_core.h"
 #include "tgms_cut_core.h"
 #include "tgms_dilate_core.h"
+#include "tgms_field_core.h"
 #include "tgms_neighbors_core.h"
 #include "tgms_separation_core.h"
 #include "tgms_rate_core.h"
@@ -577,6 +578,101 @@ void clearance(int32_t B, const int32_t* so, const double* T, const double* C, i
         if (count) count[i] = ct;
         if (tested) tested[i] = (fl & TGMS_SEP_NONFINITE) ? 0 : row.tested;
         if (flags) flags[i] = cl::row_flags(fl, bad_obstacle);
+    }
+}
+
+void field_clearance(int32_t B, const int32_t* so, const double* T, const double* C, const tgms_field& fld,
+                     const float* values, double lip, double r_min, double tol, int32_t max_evals, double* near,
+                     int32_t* evals, int32_t* flags) {
+    namespace fd = tgms::field;
+    const fd::Grid g = fd::make_grid(fld);
+    double L = lip;
+    if (lip == 0.0) {
+        double m[3] = {0.0, 0.0, 0.0};
+        const int64_t total = (int64_t)fld.n[0] * fld.n[1] * fld.n[2];
+        for (int64_t e = 0; e < total; ++e) fd::edge_max(values, fld.n, e, m);
+        L = fd::lipschitz(m, g.ih);
+    }
+    for (int32_t b = 0; b < B; ++b) {
+        const int M = so[b + 1] - so[b];
+        const double* Tb = T + so[b];
+        bool bad = M < 1 || M > TGMS_MAX_SEGMENTS, unresolved = false;
+        double c[TGMS_MAX_SEGMENTS][3][8], V[TGMS_MAX_SEGMENTS], A[TGMS_MAX_SEGMENTS], kn[TGMS_MAX_SEGMENTS + 1];
+        double fk[TGMS_MAX_SEGMENTS + 1], jump[TGMS_MAX_SEGMENTS], chk = 0.0, best = HUGE_VAL, at = 0.0, D = 0.0;
+        int32_t n = 0;
+        for (int m = 0; !bad && m < M; ++m) {
+            bad = bad || !(Tb[m] > 0.0);
+            chk = __builtin_fma(Tb[m], 0.0, chk);
+            kn[m] = D;
+            D += Tb[m];
+            const double* cm = C + ((int64_t)so[b] + m) * 24;
+            for (int q = 0; q < 24; ++q) c[m][q / 8][q % 8] = cm[q];
+            fd::speed_bounds(c[m], Tb[m], V[m], A[m], chk);
+        }
+        bad = bad || !finite(chk) || !finite(D);
+        if (!bad) {
+            // the knots: every segment's left end, the last one's right end; the jumps between them
+            for (int m = 0; m <= M; ++m) {
+                double p[3];
+                if (m < M) {
+                    p[0] = c[m][0][0], p[1] = c[m][1][0], p[2] = c[m][2][0];
+                } else {
+                    fd::position(c[M - 1], Tb[M - 1], p);
+                }
+                if (m > 0 && m < M) {
+                    double e[3];
+                    fd::position(c[m - 1], Tb[m - 1], e);
+                    jump[m - 1] = sqrt((p[0] - e[0]) * (p[0] - e[0]) + (p[1] - e[1]) * (p[1] - e[1]) +
+                                       (p[2] - e[2]) * (p[2] - e[2]));
+                }
+                fk[m] = fd::phi(g, values, p);
+                bad = bad || !finite(fk[m]);
+                if (fk[m] < best) {
+                    best = fk[m];
+                    at = m < M ? kn[m] : kn[M - 1] + Tb[M - 1];
+                }
+            }
+            jump[M - 1] = 0.0;
+            n = M + 1;
+            unresolved = n > max_evals;
+        }
+        for (int m = 0; !bad && !unresolved && m < M; ++m) {
+            if (fd::ends_rule_out(fk[m], fk[m + 1] - L * jump[m], L, V[m], Tb[m], fd::threshold(best, tol, r_min)))
+                continue;
+            int level = 0;
+            uint64_t index = 0;
+            for (bool more = true; more;) {
+                if (n >= max_evals) {
+                    unresolved = true;
+                    break;
+                }
+                double hwu, speed;
+                const double u = fd::centre(level, index, hwu);
+                const double f = fd::eval(g, values, c[m], u * Tb[m], speed);
+                ++n;
+                if (!finite(f)) {
+                    bad = true;
+                    break;
+                }
+                if (f < best) {
+                    best = f;
+                    at = kn[m] + u * Tb[m];
+                }
+                if (f - L * fd::reach(V[m], A[m], speed, hwu * Tb[m]) >= fd::threshold(best, tol, r_min)) {
+                    more = fd::advance(level, index);
+                } else if (level < fd::MAX_LEVEL) {
+                    fd::descend(level, index);
+                } else {
+                    unresolved = true;
+                    break;
+                }
+            }
+        }
+        double rec[TGMS_SEP_STRIDE];
+        const int fl = fd::finish(best, at, D, bad, unresolved, r_min, rec);
+        if (near) std::copy(rec, rec + TGMS_SEP_STRIDE, near + (int64_t)b * TGMS_SEP_STRIDE);
+        if (evals) evals[b] = (fl & TGMS_SEP_NONFINITE) ? 0 : n;
+        if (flags) flags[b] = fl;
     }
 }
 

@@ -79,6 +79,14 @@ void clearance(int32_t B, const int32_t* seg_offsets, const double* seg_times, c
                const double* obstacles, const double* scale, double r_min, double* near, int32_t* obs, int32_t* count,
                int32_t* tested, int32_t* flags);
 
+// The distance-field clearance (include/tgms.h tgms_field_clearance_batch) of a whole batch, row by
+// row: the knots, then each segment's interval tree of tgms_field_core.h, one after the other
+// with the row's least value carried along.  lip == 0: the bound is reduced from the values
+// first.  Every output is nullable.
+void field_clearance(int32_t B, const int32_t* seg_offsets, const double* seg_times, const double* coeffs,
+                     const tgms_field& field, const float* values, double lip, double r_min, double tol,
+                     int32_t max_evals, double* near, int32_t* evals, int32_t* flags);
+
 // The corridor containment (include/tgms.h tgms_corridor_batch) of a whole batch, trajectory by
 // trajectory: per segment and face the item of tgms_corridor_core.h, the segment's fold in face
 // order, the trajectory's fold left to right.  face_offsets NULL: all F faces apply to every

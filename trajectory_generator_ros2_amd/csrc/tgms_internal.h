@@ -232,4 +232,14 @@ hipError_t launch_clearance(int32_t B, const int32_t* seg_offsets, const double*
                             const double* obstacles, const double (&scale)[3], double r_min, void* scratch,
                             double* near, int32_t* obs, int32_t* count, int32_t* tested, int32_t* flags,
                             hipStream_t stream);
+
+// Distance-field clearance (tgms_field.hip): per trajectory the least value of the field
+// `values` on the grid `fld` along it (near [B][TGMS_SEP_STRIDE]), the evaluations it took
+// (evals [B]) and flags [B]; all nullable.  scratch NULL: one launch with the Lipschitz bound
+// `lip`.  scratch (field_scratch_bytes(), 8-byte aligned): two launches before it reduce the
+// bound from the values into the scratch's first double, which the search reads.
+size_t field_scratch_bytes();
+hipError_t launch_field(int32_t B, const int32_t* seg_offsets, const double* T, const double* C, const tgms_field& fld,
+                        const float* values, double lip, double r_min, double tol, int32_t max_evals, void* scratch,
+                        double* near, int32_t* evals, int32_t* flags, hipStream_t stream);
 }  // namespace tgms

@@ -405,6 +405,29 @@ class Solver:
             raise TgmsError(st, self.last_error())
         return near, obs, count, tested, flags
 
+    def field_clearance(self, seg_offsets, seg_times, coeffs, origin, h: float, values, r_min: float, tol: float,
+                        lip: float = 0.0, max_evals: int = 1 << 20):
+        """Distance-field clearance (include/tgms.h tgms_field_clearance_batch): per trajectory the
+        least value of the voxel field `values` [nz,ny,nx] (float32, node (0,0,0) at `origin`,
+        spacing h) along it, certified to tol below r_min.  lip: a Lipschitz bound of the field,
+        0 to have it reduced from the values.  Returns (near [B,2] = d_min t_min, evals [B],
+        flags [B] of SEP_* bits and FLD_UNRESOLVED)."""
+        so = np.ascontiguousarray(seg_offsets, dtype=np.int32)
+        T = np.ascontiguousarray(seg_times, dtype=np.float64).reshape(-1)
+        C = np.ascontiguousarray(coeffs, dtype=np.float64)
+        v = np.ascontiguousarray(values, dtype=np.float32)
+        assert v.ndim == 3, "values must be [nz, ny, nx]"
+        fld = _lib.Field(origin, h, v.shape[::-1])
+        B = so.shape[0] - 1
+        near = np.full((B, _lib.SEP_STRIDE), np.nan, dtype=np.float64)
+        evals, flags = (np.full(B, -2, dtype=np.int32) for _ in range(2))
+        st = self._L.tgms_field_clearance_batch(self._h, B, _ptr(so), _ptr(T), _ptr(C), ctypes.byref(fld), _ptr(v),
+                                                float(lip), float(r_min), float(tol), int(max_evals), _ptr(near),
+                                                _ptr(evals), _ptr(flags))
+        if st != _lib.OK:
+            raise TgmsError(st, self.last_error())
+        return near, evals, flags
+
     def refine(self, seg_offsets, waypoints, seg_times, end_derivs=None, k_T: float = 1.0, eta: float = 0.1,
                iters: int = 10, coeffs: bool = True):
         """Time-allocation refinement on the GPU (include/tgms.h tgms_refine_batch).
@@ -647,6 +670,21 @@ class Solver:
                                                  _ptr(d_coeffs), int(K), _ptr(d_obstacles), _ptr(sc), float(r_min),
                                                  _ptr(d_near), _ptr(d_obs), _ptr(d_count), _ptr(d_tested),
                                                  _ptr(d_flags), ctypes.c_void_p(stream))
+        if st != _lib.OK:
+            raise TgmsError(st, self.last_error())
+
+
+    def field_clearance_device(self, B: int, d_seg_offsets, d_seg_times, d_coeffs, origin, h: float, n, d_values,
+                               lip: float, r_min: float, tol: float, max_evals: int, d_near=None, d_evals=None,
+                               d_flags=None, stream: int = 0) -> None:
+        """tgms_field_clearance_batch_device: n = (nx, ny, nz), d_values fp32 with x fastest, d_near
+        [B,2] fp64, d_evals / d_flags [B] int32 (at least one of the three); the grid, lip, r_min,
+        tol and max_evals are read now.  Capturable with lip > 0; lip == 0 uses handle scratch."""
+        fld = _lib.Field(origin, h, n)
+        st = self._L.tgms_field_clearance_batch_device(self._h, int(B), _ptr(d_seg_offsets), _ptr(d_seg_times),
+                                                       _ptr(d_coeffs), ctypes.byref(fld), _ptr(d_values), float(lip),
+                                                       float(r_min), float(tol), int(max_evals), _ptr(d_near),
+                                                       _ptr(d_evals), _ptr(d_flags), ctypes.c_void_p(stream))
         if st != _lib.OK:
             raise TgmsError(st, self.last_error())
 

@@ -52,6 +52,20 @@ def ragged_batch(B: int, m_lo: int = 2, m_hi: int = 16, seed: int = SEED):
     return so.astype(np.int32), W, T
 
 
+def box_field(obstacles, origin, h: float, n):
+    """The exact unsigned distance to a set of axis-aligned boxes `obstacles` [K,6] = lo[3] hi[3]
+    (0 inside), sampled at the nodes origin + h (i, j, k) of a grid of n = (nx, ny, nz) nodes.
+    Returns float32 [nz, ny, nx], x fastest, as tgms_field_clearance_batch takes it."""
+    ob = np.asarray(obstacles, dtype=np.float64).reshape(-1, 6)
+    nx, ny, nz = (int(x) for x in n)
+    ax = [float(origin[a]) + float(h) * np.arange(m) for a, m in enumerate((nx, ny, nz))]
+    d2 = np.full((nz, ny, nx), np.inf)
+    for lo_hi in ob:
+        g = [np.maximum(np.maximum(lo_hi[a] - ax[a], ax[a] - lo_hi[3 + a]), 0.0) ** 2 for a in range(3)]
+        np.minimum(d2, g[2][:, None, None] + g[1][None, :, None] + g[0][None, None, :], out=d2)
+    return np.sqrt(d2).astype(np.float32)
+
+
 def box_corridor(seg_offsets, waypoints, width: float):
     """The simplest corridor of a batch: per segment the bounding box of its two waypoints grown
     by `width` on every side, as six axis-aligned faces +x -x +y -y +z -z (n[3] d, inside when
