@@ -3,7 +3,7 @@ the gfx950 code object of build/tgms_rate.hip.o as tests/test_kernel_resources.p
 kernels'.  The 26 coefficients of the stationarity polynomial and the 25 slots of its ladder are
 meant to be registers with compile-time indices at one wave per SIMD: every kernel in the object
 must run without scratch memory, without a spilled VGPR, and within the 512 registers a lane has
-there (k_rate: 222 VGPRs, no AGPR)."""
+there (k_rate: 308 VGPRs, 52 AGPRs)."""
 from test_kernel_resources import _kernels
 
 

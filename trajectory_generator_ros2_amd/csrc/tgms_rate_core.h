@@ -22,6 +22,15 @@
 //   - Candidates.  u = 0, u = 1 and the 25 slots of bounds::Ladder<25, 25> on G.  The ladder's
 //     level factors bounds::ffact(n, m) are no longer exact in fp64 above n = 18; the rounded
 //     factor is still positive, so no sign and no root moves.
+//   - Polish.  G's 26 coefficients are convolved twice in fp64 in the monomial basis.  Where the
+//     axis polynomials oscillate (Chebyshev-like input) they reach 1e34 while |G| near a root is
+//     below 1e16: Horner's rounding then moves a located root by 1e-3 in u, and where omega is
+//     sharply peaked the value there is 2e-3 short.  So every slot is the start of a
+//     golden-section ascent of omega^2 itself, evaluated from the axis polynomials, on the
+//     bracket that reaches half way to the neighbouring slots (POLISH steps: 0.618^40 = 4e-9 of
+//     the bracket, and omega^2 is stationary at the maximum).  A polished point replaces nothing:
+//     it is one more candidate, so the result can only rise towards the true maximum, and a slot
+//     that was exact already stays the winner unless a polished value is strictly larger.
 //   - Values.  Every value is evaluated from the axis polynomials at the candidate: f = E(u) /
 //     T^2 with g added to z after the Horner chain, p''' = E'(u) / T^3 by a Horner chain on the
 //     same coefficients, the cross product, the two sums of squares and the quotient; never from
@@ -49,6 +58,7 @@ namespace rate {
 constexpr int N = thrust::N;  // 5: degree of an axis of E
 constexpr int DC = 2 * N - 2;  // 8: degree of a component of E x E'
 constexpr int DG = 25;         // degree of G
+constexpr int POLISH = 40;     // golden-section steps per slot
 
 // E'(u) of one axis: the Horner chain on k e_k.
 TGMS_HD double dhorner(const double (&e)[N + 1], double u) {
@@ -68,6 +78,33 @@ TGMS_HD double omega2_at(const double (&e)[3][N + 1], double iT2, double iT3, do
     const double n2 = __builtin_fma(cz, cz, __builtin_fma(cy, cy, cx * cx));
     const double d = __builtin_fma(z, z, __builtin_fma(y, y, x * x));
     return n2 == 0.0 ? 0.0 : n2 / (d * d);
+}
+
+// Golden-section ascent of omega^2 on [lo, hi]: the larger of the two interior points left after
+// POLISH steps, one evaluation per step.  lo >= hi (a duplicate slot) returns at once with v < 0.
+TGMS_HD void polish(const double (&e)[3][N + 1], double iT2, double iT3, double g, double lo, double hi, double& u,
+                    double& v) {
+    constexpr double PHI = 0.6180339887498949;
+    u = lo;
+    v = -1.0;
+    if (!(hi > lo)) return;
+    double a = lo, b = hi;
+    double c = b - PHI * (b - a), d = a + PHI * (b - a);
+    double fc = omega2_at(e, iT2, iT3, g, c), fd = omega2_at(e, iT2, iT3, g, d);
+    for (int it = 0; it < POLISH; ++it) {
+        const bool left = fc > fd;  // the maximum is in [a, d]; else in [c, b]
+        b = left ? d : b;
+        a = left ? a : c;
+        const double x = left ? b - PHI * (b - a) : a + PHI * (b - a);
+        const double fx = omega2_at(e, iT2, iT3, g, x);
+        const double oc = c, ofc = fc;
+        c = left ? x : d;
+        fc = left ? fx : fd;
+        d = left ? oc : x;
+        fd = left ? ofc : fx;
+    }
+    u = fc > fd ? c : d;
+    v = fc > fd ? fc : fd;
 }
 
 // The 26 coefficients of G of one segment: c [3][8] on t in [0, T].
@@ -156,6 +193,15 @@ TGMS_HD void rate_item(const double* c, double T, double g, Item& it) {
     for (int j = 0; j <= DG; ++j) {
         const double u = j < DG ? s[j] : 1.0;
         v = omega2_at(e, iT2, iT3, g, u);
+        chk = __builtin_fma(v, 0.0, chk);
+        it.u = v > it.w2 ? u : it.u;
+        it.w2 = v > it.w2 ? v : it.w2;
+    }
+    TGMS_UNROLL
+    for (int j = 0; j < DG; ++j) {  // the slots polished: candidates added, none replaced
+        const double lo = 0.5 * ((j > 0 ? s[j - 1] : 0.0) + s[j]), hi = 0.5 * (s[j] + (j < DG - 1 ? s[j + 1] : 1.0));
+        double u;
+        polish(e, iT2, iT3, g, lo, hi, u, v);
         chk = __builtin_fma(v, 0.0, chk);
         it.u = v > it.w2 ? u : it.u;
         it.w2 = v > it.w2 ? v : it.w2;
