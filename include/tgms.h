@@ -46,7 +46,8 @@
  *     capturing.
  *     tgms_extrema_batch_device, tgms_bounds_batch_device, tgms_thrust_batch_device,
  *     tgms_rate_batch_device, tgms_dilate_batch_device and tgms_corridor_batch_device (one kernel, no plan, no scratch) may be captured for any
- *     batch, ragged included;
+ *     batch, ragged included; so may tgms_field_occupancy_device and
+ *     tgms_corridor_inflate_batch_device (no plan, no scratch);
  *   - there is no CPU fallback: with no usable GPU, tgms_create fails with
  *     TGMS_ERR_NO_DEVICE.  A GPU-less node asks for the host backend explicitly
  *     (tgms_create_host: solve + sample on the CPU, config 1).
@@ -117,7 +118,7 @@ tgms_status tgms_create(tgms_handle** out, int device);
 /* The explicit host backend (BASELINE config 1: a ROS 2 node with no GPU; the reference
  * generates on the executor thread's CPU, src/TrajectoryGenerator.cpp:54-57, :71).  A host
  * handle runs tgms_solve_batch (reduced method), tgms_sample_batch, tgms_extrema_batch,
- * tgms_bounds_batch, tgms_thrust_batch, tgms_rate_batch, tgms_dilate_batch, tgms_corridor_batch, tgms_corridor_split_batch, tgms_cut_batch, tgms_separation_batch, tgms_neighbors_batch, tgms_clearance_batch and tgms_field_clearance_batch on the calling thread with the GPU path's conventions; every other entry point returns
+ * tgms_bounds_batch, tgms_thrust_batch, tgms_rate_batch, tgms_dilate_batch, tgms_corridor_batch, tgms_corridor_split_batch, tgms_cut_batch, tgms_separation_batch, tgms_neighbors_batch, tgms_clearance_batch, tgms_field_clearance_batch and tgms_corridor_inflate_batch on the calling thread with the GPU path's conventions; every other entry point returns
  * TGMS_ERR_UNSUPPORTED on it.  Chosen by the caller only: tgms_create never falls back to
  * it. */
 tgms_status tgms_create_host(tgms_handle** out);
@@ -1011,6 +1012,85 @@ tgms_status tgms_cut_batch(tgms_handle* h, int32_t B, const int32_t* seg_offsets
                            const double* t_cut, double min_frac, int32_t* seg_offsets_out, double* waypoints_out,
                            double* seg_times_out, double* end_derivs_out, double* coeffs_out, int32_t* parent,
                            double* t0_out, int64_t* totals, int32_t* flags);
+
+/* ---- corridor inflation: the largest free box per segment from a voxel map ----
+ * The first step of the corridor loop: map -> corridors -> solve -> containment -> split -> solve.
+ * Per leg of a waypoint path the call grows an axis-aligned box on the lattice of a tgms_field
+ * until the map stops it, and returns it as six faces in exactly the layout that
+ * tgms_corridor_batch and tgms_corridor_split_batch take.  The result is integers and six
+ * doubles per segment with stated rounding: it does not depend on the algorithm, the launch
+ * shape or the order of processing, and the host backend and the device agree to the bit.
+ *   Free nodes.  Node (i, j, k) is free when values[node] >= (float)r_free, compared in fp32;
+ * a NaN node is not free.  The trilinear interpolant on a cell lies between the least and the
+ * greatest of its eight nodes, so a lattice box [lo_a .. hi_a] whose nodes are all free has
+ * phi(p) >= (float)r_free at every point of origin + h [lo, hi], phi as in the field-clearance
+ * call.  That is the certificate.
+ *   The table.  tgms_field_occupancy_device turns (values, r_free) into a summed-volume table
+ * [(nz+1)][(ny+1)][(nx+1)] int32, x fastest, caller-owned: table[k][j][i] is the number of
+ * non-free nodes with index below (i, j, k) on every axis, so the planes i = 0, j = 0, k = 0 are
+ * zero.  With it the non-free nodes of any lattice box are eight loads.  The table belongs to a
+ * (map, r_free) pair; the caller rebuilds it when either changes.
+ *   Seed.  Segment s of trajectory b joins waypoint rows s + b and s + b + 1 of d_waypoints
+ * [S+B][3].  Per axis, mn the smaller and mx the larger coordinate of the two:
+ *     lo_a = floor((mn - origin_a) / h), then lo_a -= 1 if origin_a + h lo_a > mn
+ *     hi_a = ceil((mx - origin_a) / h),  then hi_a += 1 if origin_a + h hi_a < mx
+ * every operation a separately rounded IEEE fp64 operation, no fused multiply-add.  Any
+ * axis-aligned lattice box that holds both waypoints holds the seed.
+ *   Growth.  Up to max_grow rounds; a round visits the six directions in the order +x -x +y -y
+ * +z -z, each seeing the box as the directions before it left it.  An open direction closes for
+ * good when its next layer lies off the grid, or when the slab -- that layer across the box's
+ * current extent on the other two axes -- holds a node that is not free; otherwise the box takes
+ * the layer.  Growth ends when all six directions are closed or after max_grow rounds.
+ *   Outputs per segment, each nullable, at least one given:
+ *     d_box [S][6] int32       lo[3] hi[3]
+ *     d_faces [6S][4] fp64     n[3] d in the order +x -x +y -y +z -z, inside when n . p <= d:
+ *                              +a: n = +e_a, d = origin_a + h hi_a;  -a: n = -e_a,
+ *                              d = -(origin_a + h lo_a); the product and the sum each rounded
+ *     d_face_offsets [S+1]     int64, 6 s
+ *     d_seg_flags [S] int32
+ * and per trajectory d_flags [B], the OR of its segments' flags:
+ *     TGMS_INF_BLOCKED   the seed itself holds a non-free node: no axis-aligned free box exists
+ *                        for this leg and the planner must subdivide it.  Box and faces are the
+ *                        seed's; nothing is grown.
+ *     TGMS_INF_OUTSIDE   the seed leaves the grid on some axis.  d_box = six TGMS_NEAR_NONE; the
+ *                        faces are the waypoints' own bounding box (d = mx, d = -mn).
+ *     TGMS_INF_CAPPED    some direction was still open after max_grow rounds.
+ *     TGMS_FEAS_NONFINITE alone: a waypoint of the segment is not finite (box = TGMS_NEAR_NONE,
+ *                        all 24 face entries NaN; the neighbouring segments are unaffected), or, in
+ *                        the device call, the trajectory's segment count is outside
+ *                        1..TGMS_MAX_SEGMENTS: nothing is read for it and its segment rows are not
+ *                        written, as in the corridor call.
+ * d_face_offsets[s] is written by segment s, the closing entry [S] by the last segment of
+ * trajectory B - 1.
+ *   TGMS_ERR_INVALID_ARG: an n_a < 2; h or an origin component not finite; h <= 0;
+ * (nx+1)(ny+1)(nz+1) > 2^31 - 1; r_free not finite; max_grow < 0; a NULL input; every output
+ * NULL; an fp64 or int64 array that is not 16-byte aligned.  B == 0 is TGMS_OK and launches
+ * nothing.
+ *   Neither device call uses handle scratch or a host plan; both may be captured into a HIP
+ * graph (three launches for the table, one for the boxes).  On a multi handle both run on
+ * device 0; on a host handle they return TGMS_ERR_UNSUPPORTED and tgms_corridor_inflate_batch
+ * computes on the calling thread from the same core.  On a GPU handle the host-pointer call
+ * uploads the values with the batch, builds the table in the handle's workspace, launches and
+ * downloads; a caller with a large map keeps map and table on the device. */
+#define TGMS_INF_BLOCKED 1 /* the seed holds a non-free node: box and faces are the seed's */
+#define TGMS_INF_OUTSIDE 2 /* the seed leaves the grid: no box, the faces are the waypoints' bounding box */
+#define TGMS_INF_CAPPED 4  /* a direction was still open after max_grow rounds */
+/* TGMS_FEAS_NONFINITE (16) and TGMS_NEAR_NONE (-1) are reused */
+tgms_status tgms_field_occupancy_device(tgms_handle* h, const tgms_field* field /* host */, const float* d_values,
+                                        double r_free, int32_t* d_table /* [(nz+1)][(ny+1)][(nx+1)] */,
+                                        void* stream);
+tgms_status tgms_corridor_inflate_batch_device(tgms_handle* h, int32_t B, const int32_t* d_seg_offsets,
+                                               const double* d_waypoints /* [S+B][3] */,
+                                               const tgms_field* field /* host */, const int32_t* d_table,
+                                               int32_t max_grow, int32_t* d_box /* [S][6], nullable */,
+                                               double* d_faces /* [6S][4], nullable */,
+                                               int64_t* d_face_offsets /* [S+1], nullable */,
+                                               int32_t* d_seg_flags /* [S], nullable */,
+                                               int32_t* d_flags /* [B], nullable */, void* stream);
+tgms_status tgms_corridor_inflate_batch(tgms_handle* h, int32_t B, const int32_t* seg_offsets,
+                                        const double* waypoints, const tgms_field* field, const float* values,
+                                        double r_free, int32_t max_grow, int32_t* box, double* faces,
+                                        int64_t* face_offsets, int32_t* seg_flags, int32_t* flags);
 
 /* ---- multi-GPU ----
  * One process drives devices 0 .. device_count-1 through one handle that owns one RCCL

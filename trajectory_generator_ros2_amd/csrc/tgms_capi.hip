@@ -2791,6 +2791,104 @@ tgms_status tgms_field_clearance_batch(tgms_handle* h, int32_t B, const int32_t*
     return s != TGMS_OK ? s : out.download(h);
 }
 
+// ---- corridor inflation: the largest free box per segment from a voxel map ----
+
+// The grid rules of the occupancy table (include/tgms.h): the field-clearance call's, with the
+// table's entries in place of the nodes.
+static tgms_status check_inflate_field(tgms_handle* h, const tgms_field* field) {
+    if (!field) return set_err(h, TGMS_ERR_INVALID_ARG, "field NULL");
+    int64_t total = 1;
+    for (int a = 0; a < 3; ++a) {
+        if (field->n[a] < 2) return set_err(h, TGMS_ERR_INVALID_ARG, "a field needs at least 2 nodes per axis");
+        if (!std::isfinite(field->origin[a])) return set_err(h, TGMS_ERR_INVALID_ARG, "field origin must be finite");
+        total *= (int64_t)field->n[a] + 1;  // < 2^64 after two factors, checked before the third
+        if (total > INT32_MAX) return set_err(h, TGMS_ERR_INVALID_ARG, "the table holds at most 2^31 - 1 entries");
+    }
+    if (!(field->h > 0.0) || !std::isfinite(field->h)) return set_err(h, TGMS_ERR_INVALID_ARG, "h must be finite and > 0");
+    return TGMS_OK;
+}
+
+static size_t inflate_table_entries(const tgms_field& f) {
+    return ((size_t)f.n[0] + 1) * ((size_t)f.n[1] + 1) * ((size_t)f.n[2] + 1);
+}
+
+// What both inflation calls check before they look at a pointer to the batch.
+static tgms_status check_inflate(tgms_handle* h, int32_t B, const tgms_field* field, const void* map, int32_t max_grow,
+                                 const void* box, const void* faces, const void* fo, const void* seg_flags,
+                                 const void* flags) {
+    if (B < 0) return set_err(h, TGMS_ERR_INVALID_ARG, "bad B");
+    if (tgms_status s = check_inflate_field(h, field); s != TGMS_OK) return s;
+    if (!map) return set_err(h, TGMS_ERR_INVALID_ARG, "values or table NULL");
+    if (max_grow < 0) return set_err(h, TGMS_ERR_INVALID_ARG, "max_grow must be >= 0");
+    if (!box && !faces && !fo && !seg_flags && !flags) return set_err(h, TGMS_ERR_INVALID_ARG, "every output is NULL");
+    return TGMS_OK;
+}
+
+tgms_status tgms_field_occupancy_device(tgms_handle* h, const tgms_field* field, const float* d_values, double r_free,
+                                        int32_t* d_table, void* stream) {
+    if (tgms_status e = enter(h, __func__); e != TGMS_OK) return e;
+    if (tgms_status s = check_inflate_field(h, field); s != TGMS_OK) return s;
+    if (!std::isfinite(r_free)) return set_err(h, TGMS_ERR_INVALID_ARG, "r_free must be finite");
+    if (!d_values || !d_table) return set_err(h, TGMS_ERR_INVALID_ARG, "NULL device pointer");
+    if ((reinterpret_cast<uintptr_t>(d_values) | reinterpret_cast<uintptr_t>(d_table)) & 3u)
+        return set_err(h, TGMS_ERR_INVALID_ARG, "4-byte device buffers must be 4-byte aligned");
+    TGMS_HIP(h, hipSetDevice(h->device));
+    TGMS_HIP(h, tgms::launch_field_occupancy(*field, d_values, r_free, d_table, static_cast<hipStream_t>(stream)));
+    return TGMS_OK;
+}
+
+tgms_status tgms_corridor_inflate_batch_device(tgms_handle* h, int32_t B, const int32_t* d_so, const double* dW,
+                                               const tgms_field* field, const int32_t* d_table, int32_t max_grow,
+                                               int32_t* d_box, double* d_faces, int64_t* d_fo, int32_t* d_seg_flags,
+                                               int32_t* d_flags, void* stream) {
+    if (tgms_status e = enter(h, __func__); e != TGMS_OK) return e;
+    const tgms_status s = check_inflate(h, B, field, d_table, max_grow, d_box, d_faces, d_fo, d_seg_flags, d_flags);
+    if (s != TGMS_OK) return s;
+    if (B == 0) return TGMS_OK;
+    if (!d_so || !dW) return set_err(h, TGMS_ERR_INVALID_ARG, "NULL device pointer");
+    TGMS_CHECK_ALIGNED(h, dW, d_faces, d_fo);
+    TGMS_HIP(h, hipSetDevice(h->device));
+    TGMS_HIP(h, tgms::launch_inflate(B, d_so, dW, *field, d_table, max_grow, d_box, d_faces, d_fo, d_seg_flags, d_flags,
+                                     static_cast<hipStream_t>(stream)));
+    return TGMS_OK;
+}
+
+tgms_status tgms_corridor_inflate_batch(tgms_handle* h, int32_t B, const int32_t* so, const double* waypoints,
+                                        const tgms_field* field, const float* values, double r_free, int32_t max_grow,
+                                        int32_t* box, double* faces, int64_t* face_offsets, int32_t* seg_flags,
+                                        int32_t* flags) {
+    if (tgms_status e = enter(h); e != TGMS_OK) return e;
+    tgms_status s = check_offsets(h, B, so, TGMS_MAX_SEGMENTS, nullptr, nullptr);
+    if (s != TGMS_OK) return s;
+    s = check_inflate(h, B, field, values, max_grow, box, faces, face_offsets, seg_flags, flags);
+    if (s != TGMS_OK) return s;
+    if (!std::isfinite(r_free)) return set_err(h, TGMS_ERR_INVALID_ARG, "r_free must be finite");
+    if (B == 0) return TGMS_OK;
+    if (!waypoints) return set_err(h, TGMS_ERR_INVALID_ARG, "NULL pointer");
+    if (h->host) {
+        tgms::host::corridor_inflate(B, so, waypoints, *field, values, r_free, max_grow, box, faces, face_offsets,
+                                     seg_flags, flags);
+        return TGMS_OK;
+    }
+    // the map goes up with the batch and its table is built beside them, in the workspace
+    const size_t S = (size_t)so[B], n = (size_t)B;
+    const size_t N = (size_t)field->n[0] * field->n[1] * field->n[2];
+    Outputs out;
+    const auto oFaces = out.add(faces, S * 24);
+    const auto oFo = out.add(face_offsets, S + 1);
+    const auto oBox = out.add(box, S * 6), oSegFl = out.add(seg_flags, S), oFl = out.add(flags, n);
+    double* dW;
+    float* dV;
+    int32_t *dSo, *dTab;
+    s = stage(h, {input(&dW, waypoints, (S + n) * 3), input(&dV, values, N), input(&dSo, so, n + 1),
+                  output(&dTab, inflate_table_entries(*field)), output(&out)});
+    if (s != TGMS_OK) return s;
+    TGMS_HIP(h, tgms::launch_field_occupancy(*field, dV, r_free, dTab, h->stream));
+    TGMS_HIP(h, tgms::launch_inflate(B, dSo, dW, *field, dTab, max_grow, out.dev(oBox), out.dev(oFaces), out.dev(oFo),
+                                     out.dev(oSegFl), out.dev(oFl), h->stream));
+    return out.download(h);
+}
+
 // ---- multi-GPU ----
 
 tgms_status tgms_create_multi(tgms_handle** out, int device_count) {

@@ -32,6 +32,7 @@
 #include "tgms_cut_core.h"
 #include "tgms_dilate_core.h"
 #include "tgms_field_core.h"
+#include "tgms_inflate_core.h"
 #include "tgms_neighbors_core.h"
 #include "tgms_separation_core.h"
 #include "tgms_rate_core.h"
@@ -674,6 +675,63 @@ void field_clearance(int32_t B, const int32_t* so, const double* T, const double
         if (evals) evals[b] = (fl & TGMS_SEP_NONFINITE) ? 0 : n;
         if (flags) flags[b] = fl;
     }
+}
+
+void field_occupancy(const tgms_field& fld, const float* values, double r_free, int32_t* table) {
+    namespace inf = tgms::inflate;
+    const inf::Grid g = inf::make_grid(fld);
+    const float rf = (float)r_free;
+    const int32_t nx = fld.n[0], ny = fld.n[1], nz = fld.n[2];
+    for (int32_t k = 0; k <= nz; ++k) {
+        for (int32_t j = 0; j <= ny; ++j) {
+            int32_t* row = table + inf::table_index(g, 0, j, k);
+            if (j == 0 || k == 0) {
+                std::fill(row, row + nx + 1, 0);
+                continue;
+            }
+            // along x the row's own count, plus the rectangle below it in y, plus the plane below in z
+            const float* in = values + ((int64_t)(k - 1) * ny + (j - 1)) * nx;
+            const int32_t* py = table + inf::table_index(g, 0, j - 1, k);
+            const int32_t* pz = table + inf::table_index(g, 0, j, k - 1);
+            const int32_t* pyz = table + inf::table_index(g, 0, j - 1, k - 1);
+            int32_t run = 0;
+            row[0] = 0;
+            for (int32_t i = 0; i < nx; ++i) {
+                run += inf::node_free(in[i], rf) ? 0 : 1;
+                row[i + 1] = run + py[i + 1] + pz[i + 1] - pyz[i + 1];
+            }
+        }
+    }
+}
+
+void corridor_inflate(int32_t B, const int32_t* so, const double* W, const tgms_field& fld, const float* values,
+                      double r_free, int32_t max_grow, int32_t* box, double* faces, int64_t* fo, int32_t* seg_flags,
+                      int32_t* flags) {
+    namespace inf = tgms::inflate;
+    const inf::Grid g = inf::make_grid(fld);
+    std::vector<int32_t> table((size_t)(fld.n[0] + 1) * (fld.n[1] + 1) * (fld.n[2] + 1));
+    field_occupancy(fld, values, r_free, table.data());
+    for (int32_t b = 0; b < B; ++b) {
+        int32_t all = 0;
+        for (int64_t s = so[b]; s < so[b + 1]; ++s) {
+            const double* w = W + (s + b) * 3;
+            const double w0[3] = {w[0], w[1], w[2]}, w1[3] = {w[3], w[4], w[5]};
+            int32_t bx[6];
+            double fc[6];
+            const int32_t fl = inf::segment(g, table.data(), w0, w1, max_grow, bx, fc);
+            all |= fl;
+            if (box) std::copy(bx, bx + 6, box + s * 6);
+            for (int d = 0; faces && d < 6; ++d) {
+                double row[4];
+                inf::face_row(d, fc[d], row);
+                std::copy(row, row + 4, faces + (s * 6 + d) * 4);
+            }
+            if (fo) fo[s] = 6 * s;
+            if (seg_flags) seg_flags[s] = fl;
+        }
+        if (flags) flags[b] = all;
+    }
+    if (fo && B > 0) fo[so[B]] = 6 * (int64_t)so[B];
 }
 
 void corridor(int32_t B, const int32_t* so, const double* T, const double* C, int64_t F, const double* faces,

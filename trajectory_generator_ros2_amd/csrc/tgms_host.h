@@ -87,6 +87,14 @@ void field_clearance(int32_t B, const int32_t* seg_offsets, const double* seg_ti
                      const tgms_field& field, const float* values, double lip, double r_min, double tol,
                      int32_t max_evals, double* near, int32_t* evals, int32_t* flags);
 
+// The corridor inflation (include/tgms.h tgms_corridor_inflate_batch) of a whole batch: the
+// summed-volume table of the map first (field_occupancy, [(nz+1)][(ny+1)][(nx+1)]), then segment by
+// segment the seed and the growth of tgms_inflate_core.h.  Every output is nullable.
+void field_occupancy(const tgms_field& field, const float* values, double r_free, int32_t* table);
+void corridor_inflate(int32_t B, const int32_t* seg_offsets, const double* waypoints, const tgms_field& field,
+                      const float* values, double r_free, int32_t max_grow, int32_t* box, double* faces,
+                      int64_t* face_offsets, int32_t* seg_flags, int32_t* flags);
+
 // The corridor containment (include/tgms.h tgms_corridor_batch) of a whole batch, trajectory by
 // trajectory: per segment and face the item of tgms_corridor_core.h, the segment's fold in face
 // order, the trajectory's fold left to right.  face_offsets NULL: all F faces apply to every

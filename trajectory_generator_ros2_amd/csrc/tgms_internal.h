@@ -242,4 +242,15 @@ size_t field_scratch_bytes();
 hipError_t launch_field(int32_t B, const int32_t* seg_offsets, const double* T, const double* C, const tgms_field& fld,
                         const float* values, double lip, double r_min, double tol, int32_t max_evals, void* scratch,
                         double* near, int32_t* evals, int32_t* flags, hipStream_t stream);
+
+// Corridor inflation (tgms_inflate.hip).  launch_field_occupancy: the summed-volume table
+// [(nz+1)][(ny+1)][(nx+1)] of the nodes of `values` below (float)r_free, three launches.
+// launch_inflate: per segment the largest free lattice box around it (box [S][6], faces [6S][4],
+// face_offsets [S+1], seg_flags [S]) and per trajectory the OR of its segments' flags (flags
+// [B]); all nullable, one launch.  Neither uses scratch.
+hipError_t launch_field_occupancy(const tgms_field& fld, const float* values, double r_free, int32_t* table,
+                                  hipStream_t stream);
+hipError_t launch_inflate(int32_t B, const int32_t* seg_offsets, const double* W, const tgms_field& fld,
+                          const int32_t* table, int32_t max_grow, int32_t* box, double* faces, int64_t* face_offsets,
+                          int32_t* seg_flags, int32_t* flags, hipStream_t stream);
 }  // namespace tgms

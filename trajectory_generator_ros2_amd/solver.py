@@ -428,6 +428,31 @@ class Solver:
             raise TgmsError(st, self.last_error())
         return near, evals, flags
 
+    def corridor_inflate(self, seg_offsets, waypoints, origin, h: float, values, r_free: float, max_grow: int):
+        """Corridor inflation (include/tgms.h tgms_corridor_inflate_batch): per segment of the
+        waypoint paths the largest box of free nodes (value >= float32(r_free)) of the voxel field
+        `values` [nz,ny,nx] that `max_grow` rounds of growth reach from the segment's own lattice
+        bounding box.  Returns (box [S,6] = lo[3] hi[3], faces [6S,4] and face_offsets [S+1] as
+        corridor() and corridor_loop() take them, seg_flags [S] and flags [B] of INF_* bits and
+        FEAS_NONFINITE)."""
+        so = np.ascontiguousarray(seg_offsets, dtype=np.int32)
+        W = np.ascontiguousarray(waypoints, dtype=np.float64).reshape(-1, 3)
+        v = np.ascontiguousarray(values, dtype=np.float32)
+        assert v.ndim == 3, "values must be [nz, ny, nx]"
+        fld = _lib.Field(origin, h, v.shape[::-1])
+        B = so.shape[0] - 1
+        S = int(so[-1]) if B > 0 else 0
+        box = np.full((S, 6), -2, dtype=np.int32)
+        faces = np.full((6 * S, 4), np.nan, dtype=np.float64)
+        fo = np.full(S + 1, -2, dtype=np.int64)
+        seg_flags, flags = np.full(S, -2, dtype=np.int32), np.full(B, -2, dtype=np.int32)
+        st = self._L.tgms_corridor_inflate_batch(self._h, B, _ptr(so), _ptr(W), ctypes.byref(fld), _ptr(v),
+                                                 float(r_free), int(max_grow), _ptr(box), _ptr(faces), _ptr(fo),
+                                                 _ptr(seg_flags), _ptr(flags))
+        if st != _lib.OK:
+            raise TgmsError(st, self.last_error())
+        return box, faces, fo, seg_flags, flags
+
     def refine(self, seg_offsets, waypoints, seg_times, end_derivs=None, k_T: float = 1.0, eta: float = 0.1,
                iters: int = 10, coeffs: bool = True):
         """Time-allocation refinement on the GPU (include/tgms.h tgms_refine_batch).
@@ -685,6 +710,30 @@ class Solver:
                                                        _ptr(d_coeffs), ctypes.byref(fld), _ptr(d_values), float(lip),
                                                        float(r_min), float(tol), int(max_evals), _ptr(d_near),
                                                        _ptr(d_evals), _ptr(d_flags), ctypes.c_void_p(stream))
+        if st != _lib.OK:
+            raise TgmsError(st, self.last_error())
+
+    def field_occupancy_device(self, origin, h: float, n, d_values, r_free: float, d_table, stream: int = 0) -> None:
+        """tgms_field_occupancy_device: n = (nx, ny, nz), d_values fp32 with x fastest; d_table int32
+        [(nz+1),(ny+1),(nx+1)] receives the summed-volume table of the nodes below float32(r_free).
+        Three launches, no handle scratch: capturable."""
+        fld = _lib.Field(origin, h, n)
+        st = self._L.tgms_field_occupancy_device(self._h, ctypes.byref(fld), _ptr(d_values), float(r_free),
+                                                 _ptr(d_table), ctypes.c_void_p(stream))
+        if st != _lib.OK:
+            raise TgmsError(st, self.last_error())
+
+    def corridor_inflate_device(self, B: int, d_seg_offsets, d_waypoints, origin, h: float, n, d_table, max_grow: int,
+                                d_box=None, d_faces=None, d_face_offsets=None, d_seg_flags=None, d_flags=None,
+                                stream: int = 0) -> None:
+        """tgms_corridor_inflate_batch_device: d_table of field_occupancy_device for the same grid;
+        d_box [S,6] int32, d_faces [6S,4] fp64, d_face_offsets [S+1] int64, d_seg_flags [S] and d_flags
+        [B] int32 (at least one).  One launch, no handle scratch: capturable."""
+        fld = _lib.Field(origin, h, n)
+        st = self._L.tgms_corridor_inflate_batch_device(self._h, int(B), _ptr(d_seg_offsets), _ptr(d_waypoints),
+                                                        ctypes.byref(fld), _ptr(d_table), int(max_grow), _ptr(d_box),
+                                                        _ptr(d_faces), _ptr(d_face_offsets), _ptr(d_seg_flags),
+                                                        _ptr(d_flags), ctypes.c_void_p(stream))
         if st != _lib.OK:
             raise TgmsError(st, self.last_error())
 
