@@ -729,6 +729,9 @@ tgms_status tgms_rate_batch(tgms_handle* h, int32_t B, const int32_t* seg_offset
  * limit); the tilt exceeds its limit by no more than 1e-9 F / f_min rad, F the thrust record's
  * f_max.  Tight: where active != TGMS_DIL_NONE and the trajectory is not capped, the active
  * quantity is within 1e-9 relative of its limit (the tilt within the absolute bound above).
+ * Where f_min = 0 on the result (a tilt limit alone on a free-falling arc: the tilt is undefined
+ * there and F / f_min cannot be formed) a vanishing thrust counts as upright: s is finite,
+ * TGMS_FEAS_NONFINITE is not set, active is TGMS_DIL_TILT and f_z >= -1e-9 g on the output.
  *   At least one output must be non-NULL; fp64 device arrays are 16-byte aligned; B == 0 is
  * TGMS_OK and launches nothing.  tgms_dilate_batch_device is one kernel launch with no host plan
  * and no handle scratch, so it may be captured into a HIP graph for any batch.  On a multi
