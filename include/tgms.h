@@ -502,7 +502,9 @@ tgms_status tgms_clearance_batch(tgms_handle* h, int32_t B, const int32_t* seg_o
  *                segment, the right end of the last) is always evaluated, so evals >= M + 1
  *     flags[b]   TGMS_SEP_CLOSE when d_min < r_min (strict, on the stored value);
  *                TGMS_FLD_UNRESOLVED when the row would have needed more than max_evals
- *                evaluations: it stops there and only (1) holds
+ *                evaluations: it stops there and only (1) holds.  A max_evals below M + 1
+ *                skips no knot: such a row returns evals = M + 1, the least knot value and
+ *                TGMS_FLD_UNRESOLVED
  *   (1) Upper bound: d_min = phi(p(t_min)), so d_min >= m*.
  *   (2) Certificate, without TGMS_FLD_UNRESOLVED: m* >= min(d_min - tol, r_min).  So d_min is
  * within tol of the true minimum whenever d_min - tol < r_min, and a row without TGMS_SEP_CLOSE
@@ -514,7 +516,10 @@ tgms_status tgms_clearance_batch(tgms_handle* h, int32_t B, const int32_t* seg_o
  * segment (Bernstein control values) and the speed at the centre.  The cost follows how close
  * the trajectory comes, not its duration over a step.  Both guarantees hold up to
  * 1e-9 (F + L (P + h)), F the largest |value| and P the largest coordinate magnitude the
- * trajectory reaches.  No result depends on the launch shape.
+ * trajectory reaches.  No result depends on the launch shape.  The origin is taken off each
+ * segment's constant coefficient before anything is evaluated, so positions round at their size
+ * within the map, not at their distance from the world's origin: a map and a batch moved by the
+ * same shift, where origin + shift and c_0 + shift are exact, give the same bits.
  *   An unusable row (in the device call a segment count outside 1..TGMS_MAX_SEGMENTS, for which
  * nothing is read; a time that is not finite and > 0; a non-finite coefficient; a non-finite
  * evaluated value) gets TGMS_SEP_NONFINITE alone, near = NaN NaN and evals = 0.  The values are

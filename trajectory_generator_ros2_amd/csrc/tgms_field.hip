@@ -49,7 +49,7 @@ __device__ __forceinline__ double row_next(double v) { return row_ror<15>(v); } 
 
 __global__ __launch_bounds__(W64) void k_field(int32_t B, const int32_t* __restrict__ seg_offsets,
                                                const double* __restrict__ T, const double* __restrict__ C,
-                                               field::Grid g, const float* __restrict__ values, double lip,
+                                               field::Grid world, const float* __restrict__ values, double lip,
                                                const double* __restrict__ d_lip, double r_min, double tol,
                                                int32_t max_evals, double* __restrict__ near, int32_t* __restrict__ evals_out,
                                                int32_t* __restrict__ flags) {
@@ -88,6 +88,8 @@ __global__ __launch_bounds__(W64) void k_field(int32_t B, const int32_t* __restr
             c[ax][k + 1] = x.y;
         }
     }
+    if (mine) field::to_grid_frame(world, c);  // from here on positions are relative to node (0,0,0)
+    const field::Grid g = field::grid_frame(world);
     double V, A;
     field::speed_bounds(c, Ts, V, A, chk);
     bad = bad || chk != 0.0;

@@ -69,6 +69,22 @@ TGMS_HD Grid make_grid(const tgms_field& f) {
     return g;
 }
 
+// The grid's frame.  A map far from the world's origin (2^14 m, say) would leave p(t) an ulp of
+// 1.8e-12 and p - origin no better.  So both backends take the origin off each segment's constant
+// coefficient once, c_0 - origin, and evaluate in a grid whose origin is 0: the Horner chain
+// then rounds at the size of the position within the map, and a map and a trajectory moved by
+// the same exactly representable shift give the same bits.
+TGMS_HD void to_grid_frame(const Grid& g, double (&c)[3][8]) {
+    TGMS_UNROLL
+    for (int a = 0; a < 3; ++a) c[a][0] -= g.o[a];
+}
+
+TGMS_HD Grid grid_frame(Grid g) {
+    TGMS_UNROLL
+    for (int a = 0; a < 3; ++a) g.o[a] = 0.0;
+    return g;
+}
+
 TGMS_HD double lerp(double a, double b, double f) { return __builtin_fma(f, b - a, a); }  // a == b: a to the bit
 
 // phi at the point p: eight nodes, converted to fp64, blended in fp64.  A NaN coordinate

@@ -586,7 +586,7 @@ void field_clearance(int32_t B, const int32_t* so, const double* T, const double
                      const float* values, double lip, double r_min, double tol, int32_t max_evals, double* near,
                      int32_t* evals, int32_t* flags) {
     namespace fd = tgms::field;
-    const fd::Grid g = fd::make_grid(fld);
+    const fd::Grid world = fd::make_grid(fld), g = fd::grid_frame(world);
     double L = lip;
     if (lip == 0.0) {
         double m[3] = {0.0, 0.0, 0.0};
@@ -608,6 +608,7 @@ void field_clearance(int32_t B, const int32_t* so, const double* T, const double
             D += Tb[m];
             const double* cm = C + ((int64_t)so[b] + m) * 24;
             for (int q = 0; q < 24; ++q) c[m][q / 8][q % 8] = cm[q];
+            fd::to_grid_frame(world, c[m]);
             fd::speed_bounds(c[m], Tb[m], V[m], A[m], chk);
         }
         bad = bad || !finite(chk) || !finite(D);
