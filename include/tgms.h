@@ -1100,6 +1100,104 @@ tgms_status tgms_corridor_inflate_batch(tgms_handle* h, int32_t B, const int32_t
                                         double r_free, int32_t max_grow, int32_t* box, double* faces,
                                         int64_t* face_offsets, int32_t* seg_flags, int32_t* flags);
 
+/* ---- corridor subdivision: split map-blocked legs until their boxes are free ----
+ * What the corridor inflation asks of the planner when it reports TGMS_INF_BLOCKED: a leg whose
+ * own lattice bounding box holds a non-free node is halved, and halved again, down to sixteenths,
+ * until every piece has a free box or the depth runs out; the batch -- seg_offsets, waypoints and
+ * seg_times -- is rebuilt on the device, ready for tgms_corridor_inflate_batch_device.  A diagonal
+ * leg's box is much larger than the leg and halving the leg shrinks it eightfold, so most blocked
+ * legs are blocked by their box, not by their chord.  The call also tells the planner what it
+ * cannot learn otherwise: that a straight leg is certified free, or that it is not and the path
+ * needs re-routing.  The result is integers and doubles with stated rounding: the host backend
+ * and the device agree to the bit.
+ *   Inputs.  B, d_seg_offsets and d_waypoints [S+B][3] as in the inflation call (segment s of
+ * trajectory b joins rows s + b and s + b + 1); d_seg_times [S], NULL together with
+ * d_seg_times_out; the grid `field` and the table of tgms_field_occupancy_device for the same
+ * (map, r_free); max_depth in 0..4.  The host-pointer call takes values and r_free and builds the
+ * table itself.
+ *   Points.  A leg with waypoints w0, w1 has 17 points P(i), i = 0..16.  P(0) = w0 and P(16) = w1
+ * bit for bit; otherwise per axis P(i)_a = w0_a + (i / 16) (w1_a - w0_a): the difference, the
+ * product and the sum each a separately rounded IEEE fp64 operation, no fused multiply-add (i / 16
+ * is exact).  A point depends on i only, never on the depth at which it is produced.
+ *   Pieces.  Piece (k, j), 0 <= k <= 4, 0 <= j < 2^k, joins P(j 2^(4-k)) and P((j+1) 2^(4-k)).  It
+ * is clear when the seed of its two end points -- the inflation call's seed rule -- lies inside
+ * the grid and holds no non-free node.
+ *   Demand.  need(piece, D) = 1 if the piece is clear or k == D, else need(left, D) +
+ * need(right, D); need(leg, D) is that of piece (0, 0).  A leg with a waypoint coordinate or a
+ * difference w1_a - w0_a that is not finite, or whose own seed leaves the grid, is never
+ * subdivided: need = 1 for every D.
+ *   Depth.  Per trajectory D_b is the largest D in 0..max_depth with sum_s need(leg s, D) <=
+ * TGMS_MAX_SEGMENTS; D = 0 always fits.  The rule does not depend on any order of the legs, which
+ * is why it is chosen over a greedy budget.
+ *   Output.  The leaves of every leg at depth D_b, left to right, as a batch:
+ *     d_seg_offsets_out [B+1]
+ *     d_waypoints_out [S'+B][3]  the input waypoints copied bit for bit, the inserted ones P(i)
+ *     d_seg_times_out [S']       a leaf of depth k gets T_s 2^-k, an exact scaling; a leaf of depth
+ *                                0 is copied bit for bit
+ *     d_parent [S']              the input segment row of the leaf
+ *     d_seg_flags_out [S']       per leaf: TGMS_SUB_BLOCKED, TGMS_SUB_OUTSIDE or
+ *                                TGMS_FEAS_NONFINITE, else 0
+ *     d_totals [1]               S'
+ *     d_flags [B]                the OR of the trajectory's leaves' flags, with TGMS_SUB_DONE and
+ *                                TGMS_SUB_FULL
+ * d_parent, d_seg_flags_out, d_flags and the pair of times are nullable.  The caller provides
+ * min(2^max_depth S, TGMS_MAX_SEGMENTS B) segment rows and B more waypoint rows, S =
+ * seg_offsets[B].  End derivatives belong to the two ends of a trajectory, which do not move: they
+ * are not an argument.
+ *     TGMS_SUB_DONE      the trajectory gained a segment.
+ *     TGMS_SUB_FULL      D_b < max_depth: a deeper level did not fit TGMS_MAX_SEGMENTS.
+ *     TGMS_SUB_BLOCKED   a leaf is not clear although its leg could be subdivided.  Without
+ *                        TGMS_SUB_FULL (and with max_depth = 4) the chord itself comes within a
+ *                        lattice cell of a non-free node at a sixteenth of the leg: re-route.  With
+ *                        TGMS_SUB_FULL the budget ran out first.
+ *     TGMS_SUB_OUTSIDE   the leg's own seed leaves the grid; the leg is kept whole.
+ *     TGMS_FEAS_NONFINITE  a waypoint coordinate or difference of the leg is not finite; the leg
+ *                        is kept whole and the other legs of the trajectory are unaffected.
+ *   Guarantees.  (1) An output segment without a segment flag has phi(p) >= (float)r_free on its
+ * whole chord: the certificate of the inflation call applied to its seed, which holds the chord.
+ * (2) tgms_corridor_inflate_batch on the output reports TGMS_INF_BLOCKED exactly on the segments
+ * that carry TGMS_SUB_BLOCKED and (3) TGMS_INF_OUTSIDE exactly on those that carry
+ * TGMS_SUB_OUTSIDE: it recomputes the seeds from the same doubles.  (4) No result depends on the
+ * launch shape, and a repeated call gives the same bits.
+ *   In the device call a segment count outside 1..TGMS_MAX_SEGMENTS means that nothing can be read
+ * for the trajectory: it becomes the split's placeholder -- one segment with a NaN time, two NaN
+ * waypoints, parent TGMS_NEAR_NONE, segment flag and flags TGMS_FEAS_NONFINITE -- so that the
+ * output stays a valid CSR; its neighbours are unaffected.  Only such offsets can make the output
+ * exceed the capacities above; rows beyond them are then not written, so no write lands outside a
+ * buffer.
+ *   TGMS_ERR_INVALID_ARG: the grid rules of the inflation call; r_free not finite; max_depth
+ * outside 0..4; a NULL input or required output; exactly one of the two time arrays NULL; an
+ * fp64 or int64 array that is not 16-byte aligned.  Outputs must not overlap inputs.  B == 0 is
+ * TGMS_OK, writes d_seg_offsets_out[0] = 0 and d_totals = 0 and nothing else.  The device call
+ * runs five launches on `stream` (plan, the split's three for the prefix sum, write) on handle
+ * scratch that grows with B (76 bytes a trajectory): like tgms_cut_batch_device it returns
+ * TGMS_ERR_UNSUPPORTED while its stream is capturing and is ordered among the handle's other
+ * scratch users.  On a multi handle it runs on device 0; on a host handle it returns
+ * TGMS_ERR_UNSUPPORTED.  tgms_corridor_subdivide_batch on a host handle computes on the calling
+ * thread from the same core; on a GPU handle it does one upload, builds the table in the handle's
+ * workspace, launches, does one download and copies the first S' rows to the caller. */
+#define TGMS_SUB_DONE 1    /* the trajectory gained a segment */
+#define TGMS_SUB_FULL 2    /* D_b < max_depth: the next level did not fit TGMS_MAX_SEGMENTS */
+#define TGMS_SUB_BLOCKED 4 /* a leaf is not clear although its leg could be subdivided */
+#define TGMS_SUB_OUTSIDE 8 /* the leg's own seed leaves the grid: kept whole */
+/* TGMS_FEAS_NONFINITE (16) and TGMS_NEAR_NONE (-1) are reused */
+tgms_status tgms_corridor_subdivide_batch_device(tgms_handle* h, int32_t B, const int32_t* d_seg_offsets,
+                                                 const double* d_waypoints /* [S+B][3] */,
+                                                 const double* d_seg_times /* [S], nullable */,
+                                                 const tgms_field* field /* host */, const int32_t* d_table,
+                                                 int32_t max_depth, int32_t* d_seg_offsets_out /* [B+1] */,
+                                                 double* d_waypoints_out, double* d_seg_times_out /* nullable */,
+                                                 int32_t* d_parent /* nullable */,
+                                                 int32_t* d_seg_flags_out /* nullable */,
+                                                 int64_t* d_totals /* [1]: S' */, int32_t* d_flags /* [B], nullable */,
+                                                 void* stream);
+tgms_status tgms_corridor_subdivide_batch(tgms_handle* h, int32_t B, const int32_t* seg_offsets,
+                                          const double* waypoints, const double* seg_times,
+                                          const tgms_field* field, const float* values, double r_free,
+                                          int32_t max_depth, int32_t* seg_offsets_out, double* waypoints_out,
+                                          double* seg_times_out, int32_t* parent, int32_t* seg_flags_out,
+                                          int64_t* totals, int32_t* flags);
+
 /* ---- multi-GPU ----
  * One process drives devices 0 .. device_count-1 through one handle that owns one RCCL
  * communicator per device (ncclCommInitAll, rccl.h:236; RCCL is loaded here, not at

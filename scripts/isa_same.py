@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Is the gfx950 device code of two source trees the same text?
 
-    python scripts/isa_same.py PARENT_TREE [THIS_TREE] [--keep DIR] [-D MACRO ...]
+    python scripts/isa_same.py PARENT_TREE [THIS_TREE] [--keep DIR] [-D MACRO ...] [--sources all|A.hip,B.hip]
 
 Compiles each listed HIP source of both trees to device assembly with the
 build's own flags (build.HIP_FLAGS) plus ``--cuda-device-only -S``, drops the
@@ -56,7 +56,14 @@ def main():
     ap.add_argument("tree", nargs="?", default=ROOT, help="tree under test (default: this one)")
     ap.add_argument("--keep", metavar="DIR", help="keep the assembly files here (default: a temporary folder)")
     ap.add_argument("-D", dest="defines", action="append", default=[], metavar="MACRO", help="extra -D for both sides")
+    ap.add_argument("--sources", metavar="A.hip,B.hip", help="the files to compare (default: the four solve kernels' files; "
+                    "'all': every HIP source of the parent tree's build)")
     a = ap.parse_args()
+    global SOURCES
+    if a.sources == "all":
+        SOURCES = sorted(f for f in os.listdir(os.path.join(os.path.abspath(a.parent), CSRC_REL)) if f.endswith(".hip"))
+    elif a.sources:
+        SOURCES = a.sources.split(",")
     defines = ["-D" + d for d in a.defines]
     tmp = None if a.keep else tempfile.TemporaryDirectory()
     keep = a.keep or tmp.name

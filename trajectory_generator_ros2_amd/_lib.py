@@ -26,6 +26,8 @@ NEAR_NONE = -1  # tgms_neighbors_batch: nobody within r_min
 CLR_BAD_OBSTACLE = 32  # tgms_clearance_batch: an unusable obstacle was left out
 FLD_UNRESOLVED = 64  # tgms_field_clearance_batch: the row spent max_evals; only the upper bound holds
 INF_BLOCKED, INF_OUTSIDE, INF_CAPPED = 1, 2, 4  # tgms_corridor_inflate_batch, with FEAS_NONFINITE
+SUB_DONE, SUB_FULL, SUB_BLOCKED, SUB_OUTSIDE = 1, 2, 4, 8  # tgms_corridor_subdivide_batch, with FEAS_NONFINITE
+SUB_MAX_DEPTH = 4  # sixteenths of a leg
 THRUST_STRIDE = 6  # f_min t_fmin f_max t_fmax tilt_max t_tilt
 THRUST_LOW, THRUST_HIGH, THRUST_TILT = 1, 2, 4  # with FEAS_NONFINITE
 RATE_STRIDE = 2  # omega_max t_omega
@@ -54,6 +56,7 @@ EXPORTS = [
     "tgms_clearance_batch", "tgms_clearance_batch_device",
     "tgms_field_clearance_batch", "tgms_field_clearance_batch_device",
     "tgms_field_occupancy_device", "tgms_corridor_inflate_batch", "tgms_corridor_inflate_batch_device",
+    "tgms_corridor_subdivide_batch", "tgms_corridor_subdivide_batch_device",
     "tgms_thrust_batch", "tgms_thrust_batch_device",
     "tgms_rate_batch", "tgms_rate_batch_device",
     "tgms_dilate_batch", "tgms_dilate_batch_device",
@@ -222,6 +225,12 @@ def load(path: str = ""):
     L.tgms_corridor_inflate_batch_device.restype = ctypes.c_int
     L.tgms_corridor_inflate_batch.argtypes = [vp, i32, vp, vp, ctypes.POINTER(Field), vp, dbl, i32, vp, vp, vp, vp, vp]
     L.tgms_corridor_inflate_batch.restype = ctypes.c_int
+    L.tgms_corridor_subdivide_batch_device.argtypes = [vp, i32, vp, vp, vp, ctypes.POINTER(Field), vp, i32, vp, vp, vp,
+                                                       vp, vp, vp, vp, vp]
+    L.tgms_corridor_subdivide_batch_device.restype = ctypes.c_int
+    L.tgms_corridor_subdivide_batch.argtypes = [vp, i32, vp, vp, vp, ctypes.POINTER(Field), vp, dbl, i32, vp, vp, vp, vp,
+                                                vp, vp, vp]
+    L.tgms_corridor_subdivide_batch.restype = ctypes.c_int
     L.tgms_thrust_batch_device.argtypes = [vp, i32, vp, vp, vp, dbl, ctypes.POINTER(ThrustLimits), vp, vp, vp]
     L.tgms_thrust_batch_device.restype = ctypes.c_int
     L.tgms_thrust_batch.argtypes = [vp, i32, vp, vp, vp, dbl, ctypes.POINTER(ThrustLimits), vp, vp]

@@ -2889,6 +2889,98 @@ tgms_status tgms_corridor_inflate_batch(tgms_handle* h, int32_t B, const int32_t
     return out.download(h);
 }
 
+// ---- corridor subdivision: split map-blocked legs until their boxes are free ----
+
+// What both subdivision calls check before they look at a pointer to the batch.
+static tgms_status check_subdivide(tgms_handle* h, int32_t B, const tgms_field* field, const void* map,
+                                   int32_t max_depth, const void* T, const void* so_out, const void* W_out,
+                                   const void* T_out, const void* totals) {
+    if (B < 0) return set_err(h, TGMS_ERR_INVALID_ARG, "bad B");
+    if (tgms_status s = check_inflate_field(h, field); s != TGMS_OK) return s;
+    if (!map) return set_err(h, TGMS_ERR_INVALID_ARG, "values or table NULL");
+    if (max_depth < 0 || max_depth > 4) return set_err(h, TGMS_ERR_INVALID_ARG, "max_depth must be in 0..4");
+    if ((T == nullptr) != (T_out == nullptr))
+        return set_err(h, TGMS_ERR_INVALID_ARG, "seg_times and seg_times_out are NULL together or not at all");
+    if (!so_out || !totals) return set_err(h, TGMS_ERR_INVALID_ARG, "seg_offsets_out or totals is NULL");
+    if (B > 0 && !W_out) return set_err(h, TGMS_ERR_INVALID_ARG, "waypoints_out is NULL");
+    return TGMS_OK;
+}
+
+tgms_status tgms_corridor_subdivide_batch_device(tgms_handle* h, int32_t B, const int32_t* d_so, const double* dW,
+                                                 const double* dT, const tgms_field* field, const int32_t* d_table,
+                                                 int32_t max_depth, int32_t* d_so_out, double* dW_out, double* dT_out,
+                                                 int32_t* d_parent, int32_t* d_seg_flags, int64_t* d_totals,
+                                                 int32_t* d_flags, void* stream) {
+    if (tgms_status e = enter(h, __func__); e != TGMS_OK) return e;
+    const tgms_status s = check_subdivide(h, B, field, d_table, max_depth, dT, d_so_out, dW_out, dT_out, d_totals);
+    if (s != TGMS_OK) return s;
+    if (B > 0 && (!d_so || !dW)) return set_err(h, TGMS_ERR_INVALID_ARG, "NULL device pointer");
+    TGMS_CHECK_ALIGNED(h, dW, dT, dW_out, dT_out, d_totals);
+    const hipStream_t st = static_cast<hipStream_t>(stream);
+    return launch_on_scratch(h, st, __func__, "launch_subdivide", tgms::subdivide_scratch_bytes(B), [&](void* ws) {
+        return tgms::launch_subdivide(B, d_so, dW, dT, *field, d_table, max_depth, ws, d_so_out, dW_out, dT_out, d_parent,
+                                      d_seg_flags, d_totals, d_flags, st);
+    });
+}
+
+tgms_status tgms_corridor_subdivide_batch(tgms_handle* h, int32_t B, const int32_t* so, const double* waypoints,
+                                          const double* seg_times, const tgms_field* field, const float* values,
+                                          double r_free, int32_t max_depth, int32_t* so_out, double* waypoints_out,
+                                          double* seg_times_out, int32_t* parent, int32_t* seg_flags_out,
+                                          int64_t* totals, int32_t* flags) {
+    if (tgms_status e = enter(h); e != TGMS_OK) return e;
+    tgms_status s = check_offsets(h, B, so, TGMS_MAX_SEGMENTS, nullptr, nullptr);
+    if (s != TGMS_OK) return s;
+    s = check_subdivide(h, B, field, values, max_depth, seg_times, so_out, waypoints_out, seg_times_out, totals);
+    if (s != TGMS_OK) return s;
+    if (!std::isfinite(r_free)) return set_err(h, TGMS_ERR_INVALID_ARG, "r_free must be finite");
+    if (B == 0) {
+        so_out[0] = 0;
+        totals[0] = 0;
+        return TGMS_OK;
+    }
+    if (!waypoints) return set_err(h, TGMS_ERR_INVALID_ARG, "NULL pointer");
+    if (h->host) {
+        tgms::host::subdivide(B, so, waypoints, seg_times, *field, values, r_free, max_depth, so_out, waypoints_out,
+                              seg_times_out, parent, seg_flags_out, totals, flags);
+        return TGMS_OK;
+    }
+    // the map goes up with the batch and its table is built beside them, in the workspace; the
+    // outputs at the capacity of the header, of which the first S' rows go to the caller
+    const size_t S = (size_t)so[B], n = (size_t)B;
+    const size_t cap = std::min(S << max_depth, (size_t)TGMS_MAX_SEGMENTS * n);
+    const size_t N = (size_t)field->n[0] * field->n[1] * field->n[2];
+    Outputs out;
+    const auto oW = out.add(waypoints_out, (cap + n) * 3), oT = out.add(seg_times_out, cap);
+    const auto oTot = out.add(totals, 1);
+    const auto oSo = out.add(so_out, n + 1), oPar = out.add(parent, cap), oSegFl = out.add(seg_flags_out, cap),
+               oFl = out.add(flags, n);
+    double *dW, *dT;
+    float* dV;
+    int32_t *dSo, *dTab;
+    s = stage(h, {input(&dW, waypoints, (S + n) * 3), input(&dT, seg_times, S), input(&dV, values, N),
+                  input(&dSo, so, n + 1), output(&dTab, inflate_table_entries(*field)), output(&out)});
+    if (s != TGMS_OK) return s;
+    TGMS_HIP(h, tgms::launch_field_occupancy(*field, dV, r_free, dTab, h->stream));
+    s = launch_on_scratch(h, h->stream, "tgms_corridor_subdivide_batch_device", "launch_subdivide",
+                          tgms::subdivide_scratch_bytes(B), [&](void* ws) {
+                              return tgms::launch_subdivide(B, dSo, dW, dT, *field, dTab, max_depth, ws, out.dev(oSo),
+                                                            out.dev(oW), out.dev(oT), out.dev(oPar), out.dev(oSegFl),
+                                                            out.dev(oTot), out.dev(oFl), h->stream);
+                          });
+    if (s == TGMS_OK) s = out.fetch(h);
+    if (s != TGMS_OK) return s;
+    out.take(oTot, 1);
+    const size_t S1 = (size_t)totals[0];
+    out.take(oSo, n + 1);
+    out.take(oW, (S1 + n) * 3);
+    out.take(oT, S1);
+    out.take(oPar, S1);
+    out.take(oSegFl, S1);
+    out.take(oFl, n);
+    return TGMS_OK;
+}
+
 // ---- multi-GPU ----
 
 tgms_status tgms_create_multi(tgms_handle** out, int device_count) {

@@ -35,6 +35,7 @@
 #include "tgms_inflate_core.h"
 #include "tgms_neighbors_core.h"
 #include "tgms_separation_core.h"
+#include "tgms_subdivide_core.h"
 #include "tgms_rate_core.h"
 #include "tgms_thrust_core.h"
 
@@ -733,6 +734,54 @@ void corridor_inflate(int32_t B, const int32_t* so, const double* W, const tgms_
         if (flags) flags[b] = all;
     }
     if (fo && B > 0) fo[so[B]] = 6 * (int64_t)so[B];
+}
+
+void subdivide(int32_t B, const int32_t* so, const double* W, const double* T, const tgms_field& fld, const float* values,
+               double r_free, int32_t max_depth, int32_t* so_out, double* W_out, double* T_out, int32_t* parent,
+               int32_t* seg_flags, int64_t* totals, int32_t* flags) {
+    namespace inf = tgms::inflate;
+    namespace sub = tgms::subdivide;
+    const inf::Grid g = inf::make_grid(fld);
+    std::vector<int32_t> table((size_t)(fld.n[0] + 1) * (fld.n[1] + 1) * (fld.n[2] + 1));
+    field_occupancy(fld, values, r_free, table.data());
+    int64_t out = 0;
+    for (int32_t b = 0; b < B; ++b) {
+        const int64_t s0 = so[b];
+        const int M = so[b + 1] - so[b];
+        int32_t status[TGMS_MAX_SEGMENTS];
+        uint32_t reached[TGMS_MAX_SEGMENTS], clr[TGMS_MAX_SEGMENTS];
+        int sum[sub::MAX_DEPTH + 1] = {M, 0, 0, 0, 0};
+        for (int i = 0; i < M; ++i) {
+            const double* w = W + (s0 + i + b) * 3;
+            const double w0[3] = {w[0], w[1], w[2]}, w1[3] = {w[3], w[4], w[5]};
+            status[i] = sub::leg_status(g, w0, w1);
+            reached[i] = clr[i] = 1u;  // never subdivided: one leaf at every depth
+            if (status[i] == sub::LEG_OK) sub::traverse(g, table.data(), w0, w1, max_depth, reached[i], clr[i]);
+            for (int d = 1; d <= max_depth; ++d) sum[d] += sub::need(reached[i], clr[i], d);
+        }
+        const int D = sub::pick_depth(sum, max_depth);
+        int32_t all = (sum[D] > M ? TGMS_SUB_DONE : 0) | (D < max_depth ? TGMS_SUB_FULL : 0);
+        so_out[b] = (int32_t)out;
+        for (int i = 0; i < M; ++i) {
+            const double* w = W + (s0 + i + b) * 3;
+            const uint32_t leaf = sub::leaves(reached[i], D);
+            const int32_t word = sub::pack_leg(status[i], leaf, sub::blocked(reached[i], clr[i], D));
+            all |= sub::word_flags(word);
+            const int n = __builtin_popcount(word & 0xFFFF);
+            for (int q = 0; q < n; ++q, ++out) {
+                int i0, i1;
+                sub::leaf_span((uint32_t)word, q, i0, i1);
+                for (int a = 0; a < 3; ++a) W_out[(out + b) * 3 + a] = sub::point(w[a], w[3 + a], i0);
+                if (T_out) T_out[out] = sub::leaf_time(T[s0 + i], i1 - i0);
+                if (parent) parent[out] = (int32_t)(s0 + i);
+                if (seg_flags) seg_flags[out] = sub::leaf_flag(word, i0);
+            }
+            if (i == M - 1) std::copy(w + 3, w + 6, W_out + (out + b) * 3);
+        }
+        if (flags) flags[b] = all;
+    }
+    so_out[B] = (int32_t)out;
+    totals[0] = out;
 }
 
 void corridor(int32_t B, const int32_t* so, const double* T, const double* C, int64_t F, const double* faces,

@@ -95,6 +95,14 @@ void corridor_inflate(int32_t B, const int32_t* seg_offsets, const double* waypo
                       const float* values, double r_free, int32_t max_grow, int32_t* box, double* faces,
                       int64_t* face_offsets, int32_t* seg_flags, int32_t* flags);
 
+// The corridor subdivision (include/tgms.h tgms_corridor_subdivide_batch) of a whole batch,
+// trajectory by trajectory: the table first, then per leg the traversal of tgms_subdivide_core.h,
+// the trajectory's depth and its leaves.  The offsets are valid (1..TGMS_MAX_SEGMENTS); T and
+// T_out are nullable together, parent, seg_flags and flags nullable.
+void subdivide(int32_t B, const int32_t* so, const double* W, const double* T, const tgms_field& field,
+               const float* values, double r_free, int32_t max_depth, int32_t* so_out, double* W_out, double* T_out,
+               int32_t* parent, int32_t* seg_flags, int64_t* totals, int32_t* flags);
+
 // The corridor containment (include/tgms.h tgms_corridor_batch) of a whole batch, trajectory by
 // trajectory: per segment and face the item of tgms_corridor_core.h, the segment's fold in face
 // order, the trajectory's fold left to right.  face_offsets NULL: all F faces apply to every

@@ -253,4 +253,16 @@ hipError_t launch_field_occupancy(const tgms_field& fld, const float* values, do
 hipError_t launch_inflate(int32_t B, const int32_t* seg_offsets, const double* W, const tgms_field& fld,
                           const int32_t* table, int32_t max_grow, int32_t* box, double* faces, int64_t* face_offsets,
                           int32_t* seg_flags, int32_t* flags, hipStream_t stream);
+
+// Corridor subdivision (tgms_subdivide.hip): the legs whose own lattice box holds a non-free node
+// of `table` halved down to sixteenths; the new offsets, waypoints, times (T and T_out nullable
+// together), parent rows, segment flags (both nullable), totals [1] = S' and flags [B]
+// (nullable).  Five launches on `stream`: the plan per tile of launch_inflate, launch_count_scan,
+// the write; `scratch` holds subdivide_scratch_bytes(B) bytes, 256-byte aligned.  B == 0 writes
+// so_out[0] and the total.
+size_t subdivide_scratch_bytes(int32_t B);
+hipError_t launch_subdivide(int32_t B, const int32_t* seg_offsets, const double* W, const double* T,
+                            const tgms_field& fld, const int32_t* table, int32_t max_depth, void* scratch,
+                            int32_t* so_out, double* W_out, double* T_out, int32_t* parent, int32_t* seg_flags,
+                            int64_t* totals, int32_t* flags, hipStream_t stream);
 }  // namespace tgms

@@ -453,6 +453,48 @@ class Solver:
             raise TgmsError(st, self.last_error())
         return box, faces, fo, seg_flags, flags
 
+    def corridor_subdivide(self, seg_offsets, waypoints, origin, h: float, values, r_free: float,
+                           max_depth: int = _lib.SUB_MAX_DEPTH, seg_times=None):
+        """Corridor subdivision (include/tgms.h tgms_corridor_subdivide_batch): every leg whose own
+        lattice bounding box holds a non-free node of the voxel field `values` [nz,ny,nx] is halved,
+        down to 2^-max_depth of the leg, until its pieces have free boxes or the trajectory would
+        pass MAX_SEGMENTS.  Returns the new batch trimmed to its S' segments: (seg_offsets' [B+1],
+        waypoints' [S'+B,3], seg_times' [S'] (None without seg_times), parent [S'], seg_flags [S']
+        and flags [B] of SUB_* bits and FEAS_NONFINITE)."""
+        so = np.ascontiguousarray(seg_offsets, dtype=np.int32)
+        W = np.ascontiguousarray(waypoints, dtype=np.float64).reshape(-1, 3)
+        T = None if seg_times is None else np.ascontiguousarray(seg_times, dtype=np.float64).reshape(-1)
+        v = np.ascontiguousarray(values, dtype=np.float32)
+        assert v.ndim == 3, "values must be [nz, ny, nx]"
+        fld = _lib.Field(origin, h, v.shape[::-1])
+        B = so.shape[0] - 1
+        S = int(so[-1]) if B > 0 else 0
+        cap = min(S << max(0, min(int(max_depth), _lib.SUB_MAX_DEPTH)), _lib.MAX_SEGMENTS * B)
+        so2 = np.zeros(B + 1, dtype=np.int32)
+        W2 = np.zeros((cap + B, 3), dtype=np.float64)
+        T2 = None if T is None else np.zeros(cap, dtype=np.float64)
+        parent, seg_flags = np.zeros(cap, dtype=np.int32), np.zeros(cap, dtype=np.int32)
+        totals = np.zeros(1, dtype=np.int64)
+        flags = np.zeros(B, dtype=np.int32)
+        st = self._L.tgms_corridor_subdivide_batch(self._h, B, _ptr(so), _ptr(W), _ptr(T), ctypes.byref(fld), _ptr(v),
+                                                   float(r_free), int(max_depth), _ptr(so2), _ptr(W2), _ptr(T2),
+                                                   _ptr(parent), _ptr(seg_flags), _ptr(totals), _ptr(flags))
+        if st != _lib.OK:
+            raise TgmsError(st, self.last_error())
+        S2 = int(totals[0])
+        return so2, W2[:S2 + B], None if T2 is None else T2[:S2], parent[:S2], seg_flags[:S2], flags
+
+    def corridor_from_map(self, seg_offsets, waypoints, seg_times, origin, h: float, values, r_free: float,
+                          max_grow: int, max_depth: int = _lib.SUB_MAX_DEPTH):
+        """From a voxel map to what corridor_loop() takes, on host arrays: corridor_subdivide, then
+        corridor_inflate on its output.  Returns ((seg_offsets, waypoints, seg_times, faces,
+        face_offsets), (sub_flags [B], sub_seg_flags [S'], inf_seg_flags [S'], inf_flags [B])); a
+        segment with SUB_BLOCKED is the one with INF_BLOCKED and needs re-routing."""
+        so, W, T, _, sub_seg, sub_fl = self.corridor_subdivide(seg_offsets, waypoints, origin, h, values, r_free,
+                                                               max_depth, seg_times)
+        _, faces, fo, inf_seg, inf_fl = self.corridor_inflate(so, W, origin, h, values, r_free, max_grow)
+        return (so, W, T, faces, fo), (sub_fl, sub_seg, inf_seg, inf_fl)
+
     def refine(self, seg_offsets, waypoints, seg_times, end_derivs=None, k_T: float = 1.0, eta: float = 0.1,
                iters: int = 10, coeffs: bool = True):
         """Time-allocation refinement on the GPU (include/tgms.h tgms_refine_batch).
@@ -734,6 +776,23 @@ class Solver:
                                                         ctypes.byref(fld), _ptr(d_table), int(max_grow), _ptr(d_box),
                                                         _ptr(d_faces), _ptr(d_face_offsets), _ptr(d_seg_flags),
                                                         _ptr(d_flags), ctypes.c_void_p(stream))
+        if st != _lib.OK:
+            raise TgmsError(st, self.last_error())
+
+    def corridor_subdivide_device(self, B: int, d_seg_offsets, d_waypoints, origin, h: float, n, d_table,
+                                  max_depth: int, d_seg_offsets_out, d_waypoints_out, d_totals, d_seg_times=None,
+                                  d_seg_times_out=None, d_parent=None, d_seg_flags_out=None, d_flags=None,
+                                  stream: int = 0) -> None:
+        """tgms_corridor_subdivide_batch_device: d_table of field_occupancy_device for the same grid;
+        outputs at the capacity cap = min(2^max_depth S, MAX_SEGMENTS B): d_seg_offsets_out [B+1] int32,
+        d_waypoints_out [cap+B,3], d_seg_times_out [cap] (with d_seg_times, or neither), d_parent and
+        d_seg_flags_out [cap] int32, d_totals [1] int64 = S', d_flags [B] int32.  Not capturable: it
+        grows handle scratch with B."""
+        fld = _lib.Field(origin, h, n)
+        st = self._L.tgms_corridor_subdivide_batch_device(
+            self._h, int(B), _ptr(d_seg_offsets), _ptr(d_waypoints), _ptr(d_seg_times), ctypes.byref(fld),
+            _ptr(d_table), int(max_depth), _ptr(d_seg_offsets_out), _ptr(d_waypoints_out), _ptr(d_seg_times_out),
+            _ptr(d_parent), _ptr(d_seg_flags_out), _ptr(d_totals), _ptr(d_flags), ctypes.c_void_p(stream))
         if st != _lib.OK:
             raise TgmsError(st, self.last_error())
 
