@@ -47,7 +47,8 @@
  *     tgms_extrema_batch_device, tgms_bounds_batch_device, tgms_thrust_batch_device,
  *     tgms_rate_batch_device, tgms_dilate_batch_device and tgms_corridor_batch_device (one kernel, no plan, no scratch) may be captured for any
  *     batch, ragged included; so may tgms_field_occupancy_device and
- *     tgms_corridor_inflate_batch_device (no plan, no scratch);
+ *     tgms_corridor_inflate_batch_device (no plan, no scratch), and tgms_field_edt_device (its
+ *     workspace is the caller's);
  *   - there is no CPU fallback: with no usable GPU, tgms_create fails with
  *     TGMS_ERR_NO_DEVICE.  A GPU-less node asks for the host backend explicitly
  *     (tgms_create_host: solve + sample on the CPU, config 1).
@@ -65,6 +66,7 @@
 #ifndef TGMS_H
 #define TGMS_H
 
+#include <stddef.h>
 #include <stdint.h>
 
 #ifdef __cplusplus
@@ -118,7 +120,7 @@ tgms_status tgms_create(tgms_handle** out, int device);
 /* The explicit host backend (BASELINE config 1: a ROS 2 node with no GPU; the reference
  * generates on the executor thread's CPU, src/TrajectoryGenerator.cpp:54-57, :71).  A host
  * handle runs tgms_solve_batch (reduced method), tgms_sample_batch, tgms_extrema_batch,
- * tgms_bounds_batch, tgms_thrust_batch, tgms_rate_batch, tgms_dilate_batch, tgms_corridor_batch, tgms_corridor_split_batch, tgms_cut_batch, tgms_separation_batch, tgms_neighbors_batch, tgms_clearance_batch, tgms_field_clearance_batch and tgms_corridor_inflate_batch on the calling thread with the GPU path's conventions; every other entry point returns
+ * tgms_bounds_batch, tgms_thrust_batch, tgms_rate_batch, tgms_dilate_batch, tgms_corridor_batch, tgms_corridor_split_batch, tgms_cut_batch, tgms_separation_batch, tgms_neighbors_batch, tgms_clearance_batch, tgms_field_clearance_batch, tgms_corridor_inflate_batch and tgms_field_edt on the calling thread with the GPU path's conventions; every other entry point returns
  * TGMS_ERR_UNSUPPORTED on it.  Chosen by the caller only: tgms_create never falls back to
  * it. */
 tgms_status tgms_create_host(tgms_handle** out);
@@ -1197,6 +1199,61 @@ tgms_status tgms_corridor_subdivide_batch(tgms_handle* h, int32_t B, const int32
                                           int32_t max_depth, int32_t* seg_offsets_out, double* waypoints_out,
                                           double* seg_times_out, int32_t* parent, int32_t* seg_flags_out,
                                           int64_t* totals, int32_t* flags);
+
+/* ---- distance-field build: exact Euclidean transform of a voxel map ----
+ * Step zero of the map calls: the field that tgms_field_clearance_batch_device,
+ * tgms_field_occupancy_device and through it the inflation and the subdivision start from, made
+ * on the device from the occupancy grid a sensor produces.  It is the exact Euclidean distance
+ * transform: integers and one value per node with stated rounding, so the result does not depend
+ * on the algorithm, the launch shape or the order of processing, and the host backend, the device
+ * and a brute-force search over all nodes agree to the bit.
+ *   Occupied and free nodes.  d_occ [nz][ny][nx] uint8, x fastest; a node is occupied when its
+ * byte is not 0, else free.  Do(p) is the least sum_a (p_a - q_a)^2 over the occupied nodes q, in
+ * lattice units, an exact integer; Df(p) the same over the free nodes; either is TGMS_EDT_NONE
+ * when its set is empty.
+ *   Cap.  R = ceil(max_dist / h), then R += 1 if h R < max_dist, every operation a separately
+ * rounded IEEE fp64 operation; R is clipped to 32,768.  Squared distances are reported as
+ * min(D, R^2).  Because h sqrt(R^2) = h R >= max_dist, a node farther than R spacings away cannot
+ * change a value: an implementation may search a window of R nodes per axis or the whole grid, and
+ * the result does not depend on which.
+ *   Distance.  dist(D) = h * sqrt((double)D): the square root correctly rounded, the product
+ * rounded once, no fused multiply-add; dist(TGMS_EDT_NONE) = +inf.
+ *   mode 0 (unsigned).  value = (float) min(dist(Do), max_dist), d2 = min(Do, R^2).  An occupied
+ * node gets exactly 0: the convention of an unsigned field (0 inside), which is what r_free of the
+ * occupancy table expects.
+ *   mode TGMS_EDT_SIGNED.  A free node gets value = (float) min(dist(Do) - h/2, max_dist) and d2 =
+ * min(Do, R^2); an occupied node value = (float) -min(dist(Df) - h/2, max_dist) and d2 =
+ * -min(Df, R^2); the difference is rounded once.  d2 is never 0.  The half-spacing offset puts the
+ * zero level half-way between an occupied node and its free neighbour, and it keeps the field
+ * 1-Lipschitz along the axes: for two neighbours of one kind dist changes by at most h (the
+ * triangle inequality on the lattice), and an occupied node and its free neighbour have Do = Df =
+ * 1, values h/2 and -h/2, again h apart; the cap and the clamp only reduce a difference.  So every
+ * axis edge difference is at most h, G_a <= 1 in the field-clearance call and its L <= sqrt(3)
+ * holds.  Without the offset the step across the surface would be 2 h.
+ *   Outputs, each nullable, at least one given: d_values [nz][ny][nx] fp32, the tgms_field values
+ * of the other map calls; d_d2, the same shape, int32.  d_work holds
+ * tgms_field_edt_work_size(field, mode) bytes (two int32 per node: the passes ping-pong in it), is
+ * caller-owned, 4-byte aligned and may be reused once the call's work on `stream` is done.
+ *   TGMS_ERR_INVALID_ARG: an n_a < 2 or > 16,384 (3 (n - 1)^2 stays inside int32); nx ny nz >
+ * 2^31 - 1; h or an origin component not finite; h <= 0; max_dist not finite or <= 0; unknown mode
+ * bits; a NULL field, d_occ or d_work; d_values and d_d2 both NULL; d_values, d_d2 or d_work not
+ * 4-byte aligned.  tgms_field_edt_work_size returns 0 for a field or mode the call would refuse.
+ *   The device call uses no handle scratch and no host plan and may be captured into a HIP graph
+ * (three launches, six in the signed mode: the same passes on the complement).  On a multi handle
+ * it runs on device 0; on a host handle it returns TGMS_ERR_UNSUPPORTED and tgms_field_edt computes
+ * on the calling thread from the same core (tgms_edt_core.h).  On a GPU handle tgms_field_edt
+ * uploads the occupancy, runs with a workspace from the handle and downloads: for tests and
+ * tools; a planner keeps map and field on the device. */
+#define TGMS_EDT_SIGNED 1
+#define TGMS_EDT_NONE INT32_MAX
+size_t tgms_field_edt_work_size(const tgms_field* field, int32_t mode); /* bytes; 0 on a bad field */
+tgms_status tgms_field_edt_device(tgms_handle* h, const tgms_field* field /* host */,
+                                  const uint8_t* d_occ /* [nz][ny][nx], x fastest */, double max_dist, int32_t mode,
+                                  float* d_values /* [nz][ny][nx], nullable */,
+                                  int32_t* d_d2 /* the same shape, nullable */,
+                                  void* d_work /* tgms_field_edt_work_size bytes, caller-owned */, void* stream);
+tgms_status tgms_field_edt(tgms_handle* h, const tgms_field* field, const uint8_t* occ, double max_dist, int32_t mode,
+                           float* values, int32_t* d2);
 
 /* ---- multi-GPU ----
  * One process drives devices 0 .. device_count-1 through one handle that owns one RCCL

@@ -11,6 +11,7 @@ from ._lib import CUT_DONE, CUT_FINISHED, CUT_SNAPPED
 from ._lib import RATE_HIGH, RATE_STRIDE
 from ._lib import FLD_UNRESOLVED, Field
 from ._lib import INF_BLOCKED, INF_CAPPED, INF_OUTSIDE
+from ._lib import EDT_NONE, EDT_SIGNED
 from ._lib import SUB_BLOCKED, SUB_DONE, SUB_FULL, SUB_MAX_DEPTH, SUB_OUTSIDE
 from ._lib import (CLR_BAD_OBSTACLE, COR_BAD_FACE, COR_MAX_FACES, COR_OUTSIDE, COR_STRIDE, ERR_DEVICE, ERR_INVALID_ARG,
                    ERR_NO_DEVICE, ERR_NONFINITE, ERR_SINGULAR, ERR_SKIPPED,
@@ -35,4 +36,5 @@ __all__ = [
     "FLD_UNRESOLVED", "Field",
     "INF_BLOCKED", "INF_OUTSIDE", "INF_CAPPED",
     "SUB_DONE", "SUB_FULL", "SUB_BLOCKED", "SUB_OUTSIDE", "SUB_MAX_DEPTH",
+    "EDT_SIGNED", "EDT_NONE",
 ]

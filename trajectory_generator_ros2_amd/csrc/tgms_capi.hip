@@ -2981,6 +2981,75 @@ tgms_status tgms_corridor_subdivide_batch(tgms_handle* h, int32_t B, const int32
     return TGMS_OK;
 }
 
+// ---- distance-field build: exact Euclidean transform of a voxel map ----
+
+// The grid and mode rules of the transform (include/tgms.h); `h` may be NULL (the work size).
+static tgms_status check_edt_field(tgms_handle* h, const tgms_field* field, int32_t mode) {
+    if (!field) return set_err(h, TGMS_ERR_INVALID_ARG, "field NULL");
+    int64_t total = 1;
+    for (int a = 0; a < 3; ++a) {
+        if (field->n[a] < 2 || field->n[a] > 16384)
+            return set_err(h, TGMS_ERR_INVALID_ARG, "the transform takes 2..16,384 nodes per axis");
+        if (!std::isfinite(field->origin[a])) return set_err(h, TGMS_ERR_INVALID_ARG, "field origin must be finite");
+        total *= field->n[a];  // < 2^42 after three factors
+    }
+    if (total > INT32_MAX) return set_err(h, TGMS_ERR_INVALID_ARG, "a field holds at most 2^31 - 1 nodes");
+    if (!(field->h > 0.0) || !std::isfinite(field->h)) return set_err(h, TGMS_ERR_INVALID_ARG, "h must be finite and > 0");
+    if (mode & ~TGMS_EDT_SIGNED) return set_err(h, TGMS_ERR_INVALID_ARG, "unknown mode bits");
+    return TGMS_OK;
+}
+
+// What both calls check before they look at a pointer to the map.
+static tgms_status check_edt(tgms_handle* h, const tgms_field* field, const void* occ, double max_dist, int32_t mode,
+                             const void* values, const void* d2) {
+    if (tgms_status s = check_edt_field(h, field, mode); s != TGMS_OK) return s;
+    if (!(max_dist > 0.0) || !std::isfinite(max_dist))
+        return set_err(h, TGMS_ERR_INVALID_ARG, "max_dist must be finite and > 0");
+    if (!occ) return set_err(h, TGMS_ERR_INVALID_ARG, "occupancy NULL");
+    if (!values && !d2) return set_err(h, TGMS_ERR_INVALID_ARG, "values and d2 both NULL");
+    return TGMS_OK;
+}
+
+size_t tgms_field_edt_work_size(const tgms_field* field, int32_t mode) {
+    return check_edt_field(nullptr, field, mode) == TGMS_OK ? tgms::edt_work_bytes(*field) : 0;
+}
+
+tgms_status tgms_field_edt_device(tgms_handle* h, const tgms_field* field, const uint8_t* d_occ, double max_dist,
+                                  int32_t mode, float* d_values, int32_t* d_d2, void* d_work, void* stream) {
+    if (tgms_status e = enter(h, __func__); e != TGMS_OK) return e;
+    if (tgms_status s = check_edt(h, field, d_occ, max_dist, mode, d_values, d_d2); s != TGMS_OK) return s;
+    if (!d_work) return set_err(h, TGMS_ERR_INVALID_ARG, "workspace NULL");
+    if ((reinterpret_cast<uintptr_t>(d_values) | reinterpret_cast<uintptr_t>(d_d2) | reinterpret_cast<uintptr_t>(d_work)) & 3u)
+        return set_err(h, TGMS_ERR_INVALID_ARG, "4-byte device buffers must be 4-byte aligned");
+    TGMS_HIP(h, hipSetDevice(h->device));
+    TGMS_HIP(h, tgms::launch_edt(*field, d_occ, max_dist, (mode & TGMS_EDT_SIGNED) != 0, d_values, d_d2, d_work,
+                                 static_cast<hipStream_t>(stream)));
+    return TGMS_OK;
+}
+
+tgms_status tgms_field_edt(tgms_handle* h, const tgms_field* field, const uint8_t* occ, double max_dist, int32_t mode,
+                           float* values, int32_t* d2) {
+    if (tgms_status e = enter(h); e != TGMS_OK) return e;
+    if (tgms_status s = check_edt(h, field, occ, max_dist, mode, values, d2); s != TGMS_OK) return s;
+    if (h->host) {
+        tgms::host::field_edt(*field, occ, max_dist, mode, values, d2);
+        return TGMS_OK;
+    }
+    // the map goes up, the passes ping-pong in the handle's workspace, the outputs come down
+    const size_t N = (size_t)field->n[0] * field->n[1] * field->n[2];
+    Outputs out;
+    const auto oVal = out.add(values, N);
+    const auto oD2 = out.add(d2, N);
+    uint8_t* dOcc;
+    int32_t* dWork;
+    const tgms_status s = stage(h, {input(&dOcc, occ, N), output(&dWork, tgms::edt_work_bytes(*field) / sizeof(int32_t)),
+                                    output(&out)});
+    if (s != TGMS_OK) return s;
+    TGMS_HIP(h, tgms::launch_edt(*field, dOcc, max_dist, (mode & TGMS_EDT_SIGNED) != 0, out.dev(oVal), out.dev(oD2), dWork,
+                                 h->stream));
+    return out.download(h);
+}
+
 // ---- multi-GPU ----
 
 tgms_status tgms_create_multi(tgms_handle** out, int device_count) {

@@ -31,6 +31,7 @@
 #include "tgms_corridor_split_core.h"
 #include "tgms_cut_core.h"
 #include "tgms_dilate_core.h"
+#include "tgms_edt_core.h"
 #include "tgms_field_core.h"
 #include "tgms_inflate_core.h"
 #include "tgms_neighbors_core.h"
@@ -734,6 +735,31 @@ void corridor_inflate(int32_t B, const int32_t* so, const double* W, const tgms_
         if (flags) flags[b] = all;
     }
     if (fo && B > 0) fo[so[B]] = 6 * (int64_t)so[B];
+}
+
+void field_edt(const tgms_field& fld, const uint8_t* occ, double max_dist, int32_t mode, float* values, int32_t* d2) {
+    namespace e = tgms::edt;
+    const int64_t nx = fld.n[0], ny = fld.n[1], nz = fld.n[2], N = nx * ny * nz;
+    const bool is_signed = (mode & TGMS_EDT_SIGNED) != 0;
+    const e::Cap cap = e::make_cap(fld.h, max_dist);
+    const e::Conv cv = e::make_conv(fld.h, max_dist, cap, is_signed);
+    std::vector<int32_t> a((size_t)N), b((size_t)N), s((size_t)std::max(ny, nz)), t((size_t)std::max(ny, nz));
+    for (int complement = 0; complement < (is_signed ? 2 : 1); ++complement) {
+        for (int64_t r = 0; r < ny * nz; ++r) e::row_pass(occ + r * nx, (int32_t)nx, complement != 0, cap, a.data() + r * nx);
+        for (int64_t k = 0; k < nz; ++k)
+            for (int64_t i = 0; i < nx; ++i)
+                e::line_pass(a.data() + k * nx * ny + i, b.data() + k * nx * ny + i, nx, (int32_t)ny, cap.K, s.data(), t.data());
+        for (int64_t q = 0; q < nx * ny; ++q)
+            e::line_pass(b.data() + q, a.data() + q, nx * ny, (int32_t)nz, cap.K, s.data(), t.data());
+        // in the signed mode this transform is for the free nodes, the one on the complement for the occupied
+        for (int64_t node = 0; node < N; ++node) {
+            if (is_signed && (occ[node] != 0) != (complement != 0)) continue;
+            const float val = e::value(cv, a[(size_t)node]);
+            const int32_t sq = e::squared(cv, a[(size_t)node]);
+            if (values) values[node] = complement ? -val : val;
+            if (d2) d2[node] = complement ? -sq : sq;
+        }
+    }
 }
 
 void subdivide(int32_t B, const int32_t* so, const double* W, const double* T, const tgms_field& fld, const float* values,

@@ -95,6 +95,11 @@ void corridor_inflate(int32_t B, const int32_t* seg_offsets, const double* waypo
                       const float* values, double r_free, int32_t max_grow, int32_t* box, double* faces,
                       int64_t* face_offsets, int32_t* seg_flags, int32_t* flags);
 
+// The distance-field build (include/tgms.h tgms_field_edt): the row pass and the two
+// lower-envelope passes of tgms_edt_core.h over the whole grid, once more on the complement when
+// `mode` has TGMS_EDT_SIGNED, then the conversion.  values and d2 are nullable.
+void field_edt(const tgms_field& field, const uint8_t* occ, double max_dist, int32_t mode, float* values, int32_t* d2);
+
 // The corridor subdivision (include/tgms.h tgms_corridor_subdivide_batch) of a whole batch,
 // trajectory by trajectory: the table first, then per leg the traversal of tgms_subdivide_core.h,
 // the trajectory's depth and its leaves.  The offsets are valid (1..TGMS_MAX_SEGMENTS); T and

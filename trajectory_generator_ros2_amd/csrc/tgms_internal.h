@@ -254,6 +254,14 @@ hipError_t launch_inflate(int32_t B, const int32_t* seg_offsets, const double* W
                           const int32_t* table, int32_t max_grow, int32_t* box, double* faces, int64_t* face_offsets,
                           int32_t* seg_flags, int32_t* flags, hipStream_t stream);
 
+// Distance-field build (tgms_edt.hip): the exact Euclidean transform of the occupancy bytes `occ`
+// on the grid `fld` into values [nz][ny][nx] fp32 and the squared lattice distances d2 (either
+// nullable), capped at max_dist; is_signed: negative inside, with the half-spacing offset.  Three
+// launches, six when signed, ping-ponging in `work` (edt_work_bytes, 4-byte aligned).  No scratch.
+size_t edt_work_bytes(const tgms_field& fld);
+hipError_t launch_edt(const tgms_field& fld, const uint8_t* occ, double max_dist, bool is_signed, float* values,
+                      int32_t* d2, void* work, hipStream_t stream);
+
 // Corridor subdivision (tgms_subdivide.hip): the legs whose own lattice box holds a non-free node
 // of `table` halved down to sixteenths; the new offsets, waypoints, times (T and T_out nullable
 // together), parent rows, segment flags (both nullable), totals [1] = S' and flags [B]

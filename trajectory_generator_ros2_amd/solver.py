@@ -484,6 +484,29 @@ class Solver:
         S2 = int(totals[0])
         return so2, W2[:S2 + B], None if T2 is None else T2[:S2], parent[:S2], seg_flags[:S2], flags
 
+    def field_edt(self, occ, origin, h: float, max_dist: float, signed: bool = False):
+        """Distance-field build (include/tgms.h tgms_field_edt): the exact Euclidean distance
+        transform of the occupancy grid `occ` [nz,ny,nx] (uint8, occupied where not 0; node (0,0,0) at
+        `origin`, spacing h), capped at max_dist.  signed: negative inside, the zero level half a
+        spacing outside the occupied nodes.  Returns (values [nz,ny,nx] float32, as the other map
+        calls take them, d2 [nz,ny,nx] int32, the squared lattice distances capped at R^2)."""
+        o = np.ascontiguousarray(occ, dtype=np.uint8)
+        assert o.ndim == 3, "occ must be [nz, ny, nx]"
+        fld = _lib.Field(origin, h, o.shape[::-1])
+        values = np.full(o.shape, np.nan, dtype=np.float32)
+        d2 = np.zeros(o.shape, dtype=np.int32)
+        st = self._L.tgms_field_edt(self._h, ctypes.byref(fld), _ptr(o), float(max_dist),
+                                    _lib.EDT_SIGNED if signed else 0, _ptr(values), _ptr(d2))
+        if st != _lib.OK:
+            raise TgmsError(st, self.last_error())
+        return values, d2
+
+    def field_edt_work_size(self, origin, h: float, n, signed: bool = False) -> int:
+        """tgms_field_edt_work_size: the bytes of field_edt_device's workspace for a grid of n = (nx,
+        ny, nz) nodes; 0 for a grid the call refuses."""
+        fld = _lib.Field(origin, h, n)
+        return int(self._L.tgms_field_edt_work_size(ctypes.byref(fld), _lib.EDT_SIGNED if signed else 0))
+
     def corridor_from_map(self, seg_offsets, waypoints, seg_times, origin, h: float, values, r_free: float,
                           max_grow: int, max_depth: int = _lib.SUB_MAX_DEPTH):
         """From a voxel map to what corridor_loop() takes, on host arrays: corridor_subdivide, then
@@ -762,6 +785,18 @@ class Solver:
         fld = _lib.Field(origin, h, n)
         st = self._L.tgms_field_occupancy_device(self._h, ctypes.byref(fld), _ptr(d_values), float(r_free),
                                                  _ptr(d_table), ctypes.c_void_p(stream))
+        if st != _lib.OK:
+            raise TgmsError(st, self.last_error())
+
+    def field_edt_device(self, origin, h: float, n, d_occ, max_dist: float, d_work, d_values=None, d_d2=None,
+                         signed: bool = False, stream: int = 0) -> None:
+        """tgms_field_edt_device: n = (nx, ny, nz), d_occ uint8 with x fastest; d_values fp32 and d_d2
+        int32 of the same shape (at least one); d_work of field_edt_work_size bytes.  Three launches
+        (six signed), no handle scratch: capturable."""
+        fld = _lib.Field(origin, h, n)
+        st = self._L.tgms_field_edt_device(self._h, ctypes.byref(fld), _ptr(d_occ), float(max_dist),
+                                           _lib.EDT_SIGNED if signed else 0, _ptr(d_values), _ptr(d_d2), _ptr(d_work),
+                                           ctypes.c_void_p(stream))
         if st != _lib.OK:
             raise TgmsError(st, self.last_error())
 

@@ -66,6 +66,19 @@ def box_field(obstacles, origin, h: float, n):
     return np.sqrt(d2).astype(np.float32)
 
 
+def box_occupancy(obstacles, origin, h: float, n):
+    """The occupancy grid of the same boxes on the same nodes: a node is occupied when it lies in a
+    closed box.  Returns uint8 [nz, ny, nx], x fastest, as tgms_field_edt takes it."""
+    ob = np.asarray(obstacles, dtype=np.float64).reshape(-1, 6)
+    nx, ny, nz = (int(x) for x in n)
+    ax = [float(origin[a]) + float(h) * np.arange(m) for a, m in enumerate((nx, ny, nz))]
+    occ = np.zeros((nz, ny, nx), dtype=bool)
+    for lo_hi in ob:
+        g = [(ax[a] >= lo_hi[a]) & (ax[a] <= lo_hi[3 + a]) for a in range(3)]
+        occ |= g[2][:, None, None] & g[1][None, :, None] & g[0][None, None, :]
+    return occ.astype(np.uint8)
+
+
 def box_corridor(seg_offsets, waypoints, width: float):
     """The simplest corridor of a batch: per segment the bounding box of its two waypoints grown
     by `width` on every side, as six axis-aligned faces +x -x +y -y +z -z (n[3] d, inside when
