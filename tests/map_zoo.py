@@ -1,0 +1,544 @@
+"""Constructed maps for the map calls (tgms_field_edt*, tgms_field_occupancy_device,
+tgms_corridor_inflate_batch*, tgms_corridor_subdivide_batch*), shared by test_map_zoo_host.py and
+test_gpu_map_zoo.py.  edt_ref.py, inflate_ref.py and subdivide_ref.py hold the calls against
+brute-force references on small random maps; here the map is built so that the answer is a formula
+(and can be had at a size where brute force is too slow), or two code paths of one call are held
+against each other, or the same scene is placed elsewhere in a larger grid:
+    A  nodes, solid_box, complement: occupancy with exact Do and Df from closed forms
+    B  the launch seams of the EDT kernels: rows by grid-stride, the longest row, windowed stages
+    C  the EDT against itself: axis orders and reflections, embedding, one more node, the two modes
+    D  the summed-volume table: closed forms, chunk and unroll seams, axis orders
+    E  inflation and subdivision: a cavity with a known box and round count, placement, reversal
+Backend-agnostic like the three reference files: a backend is anything with field_edt(...),
+corridor_inflate(...) and corridor_subdivide(...) (a Solver has them; the GPU file wraps the device
+entry points the same way).  The table checks take the function occupancy(origin, h, values,
+r_free) -> table.
+
+Every comparison is for equality to the bit; there is no tolerance in this file."""
+import functools
+import itertools
+from collections import namedtuple
+
+import numpy as np
+
+import edt_ref as ER
+import inflate_ref as IR
+import subdivide_ref as SR
+from trajectory_generator_ros2_amd import EDT_NONE, INF_BLOCKED, INF_CAPPED, SUB_BLOCKED, SUB_DONE
+
+Map = namedtuple("Map", "occ Do Df")  # uint8 [nz, ny, nx]; int64 squares, EDT_NONE where the set is empty
+
+
+# ---- A. occupancy with closed-form answers ----
+
+def _ijk(n):
+    nx, ny, nz = n
+    k, j, i = np.indices((nz, ny, nx), dtype=np.int64)
+    return i, j, k
+
+
+def _frozen(occ, Do, Df):
+    for x in (occ, Do, Df):
+        x.setflags(write=False)
+    return Map(occ, Do, Df)
+
+
+def nodes(n, qs, byte=255):
+    """Occupied nodes qs = [(i, j, k), ...] and nothing else.  Do is the least |p - q|^2; Df is 0 off
+    the nodes and 1 on them, each node having a free neighbour along some axis (asserted)."""
+    i, j, k = _ijk(n)
+    occ = np.zeros(n[::-1], dtype=np.uint8)
+    Do = np.full(occ.shape, EDT_NONE, dtype=np.int64)
+    for q in qs:
+        occ[q[2], q[1], q[0]] = byte
+        Do = np.minimum(Do, (i - q[0]) ** 2 + (j - q[1]) ** 2 + (k - q[2]) ** 2)
+    for q in qs:
+        beside = [tuple(q[a] + s * (a == ax) for a in range(3)) for ax in range(3) for s in (-1, 1)]
+        assert any(all(0 <= b[a] < n[a] for a in range(3)) and occ[b[2], b[1], b[0]] == 0 for b in beside), q
+    return _frozen(occ, Do, (occ != 0).astype(np.int64))
+
+
+def solid_box(n, a, b, byte=1):
+    """The lattice box a..b (inclusive) occupied.  Outside, Do is the squared distance to the box:
+    per axis max(a - p, 0, p - b).  Inside, any free node lies beyond some face of the box, at
+    least (distance to that face + 1) away along that axis, and the node straight beyond the face
+    attains it; a face on the grid's edge has no free node beyond it and offers nothing."""
+    p = _ijk(n)
+    inside = np.ones(n[::-1], dtype=bool)
+    Do = np.zeros(n[::-1], dtype=np.int64)
+    best = np.full(n[::-1], EDT_NONE, dtype=np.int64)
+    for ax in range(3):
+        assert 0 <= a[ax] <= b[ax] <= n[ax] - 1
+        inside &= (p[ax] >= a[ax]) & (p[ax] <= b[ax])
+        Do += np.maximum(np.maximum(a[ax] - p[ax], 0), p[ax] - b[ax]) ** 2
+        if a[ax] > 0:
+            best = np.minimum(best, (p[ax] - a[ax] + 1) ** 2)
+        if b[ax] < n[ax] - 1:
+            best = np.minimum(best, (b[ax] - p[ax] + 1) ** 2)
+    occ = np.where(inside, np.uint8(byte), np.uint8(0))
+    return _frozen(occ, Do, np.where(inside, best, 0))
+
+
+def complement(m):
+    """Occupied and free exchanged: so are Do and Df."""
+    return _frozen((m.occ == 0).astype(np.uint8), m.Df.copy(), m.Do.copy())
+
+
+# (label, n, builder): every grid at most 20^3, so that brute force can confirm the formula
+FORMULA_CASES = [
+    ("node", (9, 7, 5), lambda n: nodes(n, [(4, 3, 2)])),
+    ("node at corner 0", (9, 7, 5), lambda n: nodes(n, [(0, 0, 0)], byte=1)),
+    ("node at corner 7", (9, 7, 5), lambda n: nodes(n, [(8, 6, 4)], byte=128)),
+    ("box inside", (12, 10, 8), lambda n: solid_box(n, (3, 2, 2), (7, 6, 4))),
+    ("box on two faces", (12, 10, 8), lambda n: solid_box(n, (0, 3, 2), (4, 9, 4), byte=7)),
+    ("box on five faces", (12, 10, 8), lambda n: solid_box(n, (0, 0, 0), (10, 9, 7))),  # all but the plane i = 11
+    ("box of one node", (9, 7, 5), lambda n: solid_box(n, (4, 3, 2), (4, 3, 2))),
+    ("two nodes, bisector on nodes", (9, 7, 5), lambda n: nodes(n, [(2, 3, 2), (6, 3, 2)])),  # the plane i = 4
+    ("two nodes, bisector between", (9, 7, 5), lambda n: nodes(n, [(2, 3, 2), (7, 3, 2)])),  # the plane i = 4.5
+    ("two nodes, oblique", (9, 7, 5), lambda n: nodes(n, [(1, 1, 0), (6, 4, 3)])),
+    ("two nodes, neighbours", (9, 7, 5), lambda n: nodes(n, [(4, 3, 2), (5, 3, 2)])),
+    ("all but one node", (9, 7, 5), lambda n: complement(nodes(n, [(4, 3, 2)]))),
+]
+
+
+def check_formula(m):
+    """The closed forms against the brute force of edt_ref.py, where both exist."""
+    assert m.occ.size <= 20 ** 3
+    assert np.array_equal(m.Do, ER.nearest_squared(m.occ != 0))
+    assert np.array_equal(m.Df, ER.nearest_squared(m.occ == 0))
+
+
+def far(n, h):
+    """A cap beyond the grid's diagonal: nothing is capped."""
+    return ER.max_dists(n, h)[1]
+
+
+def check_map(be, m, caps=(2, None), hs=ER.H_VALUES, what=""):
+    """Values and d2 of both modes equal those of the map's own Do and Df, through edt_ref.convert
+    (the header's rounding rule).  caps: R in nodes (max_dist = (R - 1/2) h, a window of R nodes)
+    or None for no cap."""
+    n = m.occ.shape[::-1]
+    for h in hs:
+        for R in caps:
+            md = far(n, h) if R is None else (R - 0.5) * h
+            assert R is None or ER.cap(h, md) == R
+            for signed in (False, True):
+                got = be.field_edt(m.occ, ER.ORIGIN, h, md, signed)
+                ER.assert_same(got, ER.convert(m.Do, m.Df, m.occ, h, md, signed), (what, n, h, R, signed))
+
+
+# ---- B. the launch seams of the EDT kernels ----
+# The constants of csrc/tgms_edt.hip as plain numbers: a wavefront per row and four per workgroup,
+# at most 2,048 workgroups, so a launch covers 8,192 rows a trip; a row in chunks of 64 nodes, 256
+# at the most; a line tile of 32 outputs staged 64 source entries at a time.
+ROWS_PER_TRIP, CHUNK, MAX_CHUNKS, LINE_TILE, LINE_STAGE = 8192, 64, 256, 32, 64
+
+STRIDE_N = (3, 91, 181)  # 16,471 rows of 3 nodes: two full trips and a third that ends in the middle of a workgroup
+
+
+def _row(n, q):
+    return q[2] * n[1] + q[1]
+
+
+@functools.lru_cache(maxsize=None)
+def stride_map(name):
+    n = STRIDE_N
+    rows = n[1] * n[2]
+    assert rows > 2 * ROWS_PER_TRIP and rows % 4 != 0
+    if name == "two nodes":  # one in the first trip, one in the last hundred rows
+        qs = [(1, 40, 0), (2, 50, 180)]
+        assert _row(n, qs[0]) < ROWS_PER_TRIP and rows - 100 <= _row(n, qs[1]) < rows
+        # the wavefront that has the first node's row meets two rows without a target afterwards
+        assert _row(n, qs[0]) + 2 * ROWS_PER_TRIP < rows
+    else:
+        assert name == "last row"
+        qs = [(0, 90, 180)]
+        assert _row(n, qs[0]) == rows - 1
+    return nodes(n, qs)
+
+
+LONG_N = (16384, 2, 2)  # the longest legal row: all 256 chunk slots
+LONG_TARGETS = {"first": (0, 0, 0), "last": (16383, 0, 0), "row 3 only": (8255, 1, 1)}
+
+
+@functools.lru_cache(maxsize=None)
+def long_map(name, inverted=False):
+    assert LONG_N[0] == CHUNK * MAX_CHUNKS
+    m = nodes(LONG_N, [LONG_TARGETS[name]])
+    return complement(m) if inverted else m
+
+
+WINDOW_SHAPES = ((3, 130, 2), (2, 3, 130))  # of edt_ref.SHAPES: the long line along y, along z
+WINDOW_MAPS = ("random_0.05", "corner0", "corner7", "checker")
+WINDOW_R = (17, 33, 63, 64, 65)
+WINDOW_CASES = [(n, m) for n in WINDOW_SHAPES for m in WINDOW_MAPS]
+
+
+def window_seam(n_line, R):
+    """Whether some tile of a line of n_line nodes has a window that starts inside the line and
+    spans more than one stage, and whether some such window ends in a short stage."""
+    hit = short = False
+    for j0 in range(0, n_line, LINE_TILE):
+        s_lo, s_hi = max(0, j0 - R), min(n_line, j0 + LINE_TILE + R)
+        if s_lo > 0 and s_hi - s_lo > LINE_STAGE:
+            hit = True
+            short = short or (s_hi - s_lo) % LINE_STAGE != 0
+    return hit, short
+
+
+def check_window(be, n, name):
+    """max_dist = R h, R from 17 to 65, on a line of 130 nodes: against the cached squares of
+    edt_ref.py.  The cap the call derives from R h is R or R + 1 (the quotient is rounded); the seam
+    is asserted for the cap it is."""
+    assert n in ER.SHAPES
+    occ = ER.make_map(n, name)
+    Do, Df = ER.squares(n, name)
+    for h in ER.H_VALUES:
+        for R in WINDOW_R:
+            md = R * h
+            cap = ER.cap(h, md)
+            assert R <= cap <= R + 1
+            assert window_seam(max(n), cap) == (True, True), (n, R, cap)
+            for signed in (False, True):
+                got = be.field_edt(occ, ER.ORIGIN, h, md, signed)
+                ER.assert_same(got, ER.convert(Do, Df, occ, h, md, signed), (n, name, h, R, signed))
+
+
+# ---- C. the EDT against itself ----
+
+C_N, C_NAME, C_H = (40, 33, 9), "random_0.05", 0.125
+C_CAPS = (11, None)
+# (order of the array's axes, axes reversed afterwards): all six orders, each also reversed along
+# every axis, and each single reversal of the map as it is
+TRANSFORMS = ([(p, f) for p in itertools.permutations(range(3)) for f in ((), (0, 1, 2))]
+              + [((0, 1, 2), (a,)) for a in range(3)])
+
+
+def transformed(x, t):
+    y = np.transpose(x, t[0])
+    return np.ascontiguousarray(np.flip(y, t[1]) if t[1] else y)
+
+
+def _c_dist(R, n=C_N):
+    return far(n, C_H) if R is None else R * C_H  # h a power of two: R h / h = R exactly
+
+
+def check_axis_orders(be, R):
+    """The distance transform commutes with a permutation or reversal of the axes.  Here that puts
+    every line of the map through the x pass (ballots on the device, two sweeps on the host) and
+    through both line passes (min-plus over LDS, the lower envelope on the host)."""
+    occ = ER.make_map(C_N, C_NAME)
+    md = _c_dist(R)
+    assert R is None or ER.cap(C_H, md) == R
+    for signed in (False, True):
+        base = be.field_edt(occ, ER.ORIGIN, C_H, md, signed)
+        ER.assert_same(base, ER.convert(*ER.squares(C_N, C_NAME), occ, C_H, md, signed), ("base", R, signed))
+        for t in TRANSFORMS:
+            got = be.field_edt(transformed(occ, t), ER.ORIGIN, C_H, md, signed)
+            ER.assert_same(got, tuple(transformed(b, t) for b in base), (t, R, signed))
+
+
+EMBED_OFFSET, EMBED_N = (5, 70, 3), (47, 105, 13)  # 64,155 nodes; the map's y lines start in the third line tile
+
+
+def check_embedding(be, R):
+    """The map at an offset in a larger grid of free nodes: no occupied node is added, so Do on the
+    original nodes is what it was."""
+    occ = ER.make_map(C_N, C_NAME)
+    ox, oy, oz = EMBED_OFFSET
+    assert all(o + m <= e for o, m, e in zip(EMBED_OFFSET, C_N, EMBED_N))
+    big = np.zeros(EMBED_N[::-1], dtype=np.uint8)
+    big[oz:oz + C_N[2], oy:oy + C_N[1], ox:ox + C_N[0]] = occ
+    md = _c_dist(R, EMBED_N)
+    base = be.field_edt(occ, ER.ORIGIN, C_H, md, False)
+    got = be.field_edt(big, ER.ORIGIN, C_H, md, False)
+    cut = tuple(g[oz:oz + C_N[2], oy:oy + C_N[1], ox:ox + C_N[0]] for g in got)
+    ER.assert_same(tuple(np.ascontiguousarray(c) for c in cut), base, ("embedded", R))
+    assert np.array_equal(got[1] == 0, big != 0)
+
+
+def check_one_more_node(be, R):
+    """Do of the map with the node q added is min(Do, |p - q|^2): never higher, and lower exactly
+    where q is nearer than every node before."""
+    occ = ER.make_map(C_N, C_NAME)
+    q = next((i, 16, 4) for i in range(20, 40) if occ[4, 16, i] == 0)
+    more = occ.copy()
+    more[q[2], q[1], q[0]] = 1
+    md = _c_dist(R)
+    R2 = ER.cap(C_H, md) ** 2
+    i, j, k = _ijk(C_N)
+    to_q = (i - q[0]) ** 2 + (j - q[1]) ** 2 + (k - q[2]) ** 2
+    before = be.field_edt(occ, ER.ORIGIN, C_H, md, False)[1]
+    after = be.field_edt(more, ER.ORIGIN, C_H, md, False)[1]
+    assert (after <= before).all()
+    assert np.array_equal(after < before, to_q < before)  # before <= R^2, so a nearer q is inside the cap
+    assert np.array_equal(after, np.minimum(before, np.minimum(to_q, R2)).astype(np.int32))
+    assert (after < before).sum() > 1
+
+
+def check_modes(be, name, md_over_h):
+    """On free nodes the signed d2 is the unsigned one; in either mode the value is the header's
+    conversion of the call's own d2 wherever |d2| < R^2 (at R^2 the square is no longer known)."""
+    occ = ER.make_map(C_N, name)
+    free = occ == 0
+    for h in ER.H_VALUES:
+        md = md_over_h * h
+        R2 = ER.cap(h, md) ** 2
+        vu, du = be.field_edt(occ, ER.ORIGIN, h, md, False)
+        vs, ds = be.field_edt(occ, ER.ORIGIN, h, md, True)
+        assert np.array_equal(ds[free], du[free]) and (ds[~free] < 0).all() and (du[~free] == 0).all()
+        d = du.astype(np.int64)
+        known = d < R2
+        assert known[free].any()
+        assert ER.same_bits(vu[known], ER.convert(d, d, occ, h, md, False)[0][known]), (name, h)
+        Do, Df = np.where(free, ds, 1).astype(np.int64), np.where(free, 1, -ds.astype(np.int64))
+        known = np.abs(ds.astype(np.int64)) < R2
+        assert known[free].any() and known[~free].any()
+        assert ER.same_bits(vs[known], ER.convert(Do, Df, occ, h, md, True)[0][known]), (name, h)
+
+
+# ---- D. the summed-volume table ----
+# csrc/tgms_inflate.hip: a wavefront per table row, 64 nodes a pass, 8,192 rows a trip; a lane per
+# line, eight entries in flight.
+TABLE_SEAMS = [(63, 3, 2), (64, 3, 2), (65, 3, 2), (128, 2, 3),  # nx around one chunk, and exactly two
+               (3, 9, 17), (3, 16, 9), (3, 17, 16),              # ny and nz around the unroll of 8
+               (2, 127, 130), (2, 126, 130)]                     # 16,768 and 16,637 table rows: three trips
+TABLE_PERM_GRIDS = [(9, 8, 7), (70, 9, 17)]
+
+
+def grid_id(n):
+    return "x".join(map(str, n))
+
+
+def check_table_closed_forms(occupancy, n):
+    """Every node non-free: entry (i, j, k) is i j k.  One non-free node q: 1 where the entry lies
+    beyond q on every axis, else 0; q at node 0, at the last node and in the middle."""
+    nx, ny, nz = n
+    k, j, i = np.indices((nz + 1, ny + 1, nx + 1), dtype=np.int64)
+    origin = (0.0, 0.0, 0.0)
+    got = occupancy(origin, 1.0, np.zeros((nz, ny, nx), np.float32), 0.3)
+    assert got.dtype == np.int32 and np.array_equal(got, i * j * k), n
+    for q in ((0, 0, 0), (nx - 1, ny - 1, nz - 1), (nx // 2, ny // 2, nz // 2)):
+        v = np.ones((nz, ny, nx), np.float32)
+        v[q[2], q[1], q[0]] = np.nan if q[0] == 0 else 0.0
+        got = occupancy(origin, 1.0, v, 0.3)
+        assert np.array_equal(got, ((i > q[0]) & (j > q[1]) & (k > q[2])).astype(np.int32)), (n, q)
+
+
+def check_table_axis_orders(occupancy, n):
+    """The table of an axis-permuted field is the permuted table: the shuffle scan along x against
+    the serial line sums along y and z."""
+    v = IR.table_values(n)
+    base = occupancy((0.0, 0.0, 0.0), 1.0, v, 0.5)
+    assert np.array_equal(base, IR.table_reference(v, 0.5))
+    for p in itertools.permutations(range(3)):
+        got = occupancy((0.0, 0.0, 0.0), 1.0, np.ascontiguousarray(np.transpose(v, p)), 0.5)
+        assert np.array_equal(got, np.transpose(base, p)), (n, p)
+
+
+# ---- E. inflation and subdivision on constructed maps ----
+
+class Reference:
+    """The NumPy references behind the backend interface: what a check asks of a backend it must
+    first get from them."""
+
+    def corridor_inflate(self, *a):
+        return IR.reference(*a)
+
+    def corridor_subdivide(self, so, W, origin, h, values, r_free, max_depth, seg_times=None):
+        return SR.reference(so, W, seg_times, origin, h, values, r_free, max_depth)
+
+
+CAV_ORIGIN, CAV_H, CAV_N, CAV_R = (-1.0, 0.5, 2.0), 0.5, (13, 11, 9), 0.3
+# (label, a, b, [(q0, q1) in lattice coordinates])
+CAVITIES = [
+    ("inside", (2, 3, 1), (10, 8, 6),
+     [((5.2, 5.7, 3.4), (6.6, 5.3, 3.9)),    # seed (5, 5, 3)..(7, 6, 4): every direction has layers to take
+      ((2.0, 4.5, 2.5), (3.5, 4.5, 2.5)),    # the seed touches the face -x: that direction closes in round 1
+      ((2.0, 3.0, 1.0), (10.0, 8.0, 6.0)),   # the cavity's diagonal: the seed is the answer, one round closes all six
+      ((10.0, 8.0, 6.0), (10.0, 8.0, 6.0)),  # a single node in the far corner
+      ((9.5, 3.25, 5.75), (2.5, 7.5, 1.5))]),
+    # flush against the faces i = 0, j = 10 and k = 0 of the grid: three directions close because
+    # their next layer is off the grid
+    ("on three faces", (0, 4, 0), (6, 10, 4),
+     [((2.2, 6.7, 1.4), (3.6, 6.3, 1.9)),
+      ((0.0, 10.0, 0.0), (0.5, 9.5, 0.5)),
+      ((0.0, 4.0, 0.0), (6.0, 10.0, 4.0)),
+      ((6.0, 4.0, 4.0), (6.0, 4.0, 4.0))]),
+]
+
+
+def cavity(a, b, legs):
+    """(values, so, W): every node non-free but the lattice box a..b; one trajectory of one leg per
+    pair of lattice points."""
+    v = np.zeros(CAV_N[::-1], dtype=np.float32)
+    v[a[2]:b[2] + 1, a[1]:b[1] + 1, a[0]:b[0] + 1] = 1.0
+    o = np.array(CAV_ORIGIN)
+    W = np.array([o + CAV_H * np.asarray(q, dtype=np.float64) for leg in legs for q in leg])
+    return v, np.arange(len(legs) + 1, dtype=np.int32), W
+
+
+def cavity_gaps(a, b, leg):
+    """The seed of a leg given in lattice coordinates (CAV_H is a power of two and CAV_ORIGIN dyadic:
+    the seed is floor and ceil exactly) and the layers between it and the cavity's faces, in the
+    order +x -x +y -y +z -z."""
+    q = np.array(leg)
+    lo, hi = np.floor(q.min(axis=0)).astype(np.int64), np.ceil(q.max(axis=0)).astype(np.int64)
+    assert (lo >= np.array(a)).all() and (hi <= np.array(b)).all()
+    return lo, hi, np.stack([np.array(b) - hi, lo - np.array(a)], axis=1).reshape(6)
+
+
+def faces_of(origin, h, lo, hi):
+    f = np.zeros((6, 4))
+    o = np.asarray(origin, dtype=np.float64)
+    for ax in range(3):
+        f[2 * ax, ax], f[2 * ax, 3] = 1.0, IR.plane(o[ax], h, hi[ax])
+        f[2 * ax + 1, ax], f[2 * ax + 1, 3] = -1.0, -IR.plane(o[ax], h, lo[ax])
+    return f
+
+
+def check_cavity(be, a, b, legs):
+    """The round count.  Inside the cavity every slab a direction tests lies in the cavity, whatever
+    the box's extent on the other two axes, so it is free until the layer leaves the cavity: a
+    direction with g layers between the seed and the cavity's face takes one in each of the rounds
+    1..g and closes in round g + 1, on the non-free layer beyond the face or because that layer is
+    off the grid.  The directions do not interact.  After max_grow rounds direction d has taken
+    min(g_d, max_grow) layers and is still open when max_grow <= g_d; TGMS_INF_CAPPED is gone from
+    max_grow = G = max_d g_d + 1 on.  At G - 1 the box is already the cavity, but the farthest
+    direction has not yet been refused a layer, and the flag is still there; at G - 2 (if any) the
+    box is a layer short.  Checked for every leg at every such count of any leg, and at 100."""
+    v, so, W = cavity(a, b, legs)
+    seeds = [cavity_gaps(a, b, leg) for leg in legs]
+    counts = sorted({max(0, int(g.max()) + 1 - back) for _, _, g in seeds for back in (0, 1, 2)} | {100})
+    for mg in counts:
+        box, faces, fo, seg_flags, flags = IR.check_equal(be, so, W, CAV_ORIGIN, CAV_H, v, CAV_R, mg)
+        for s, (lo, hi, g) in enumerate(seeds):
+            took = np.minimum(g, mg)
+            want_lo, want_hi = lo - took[1::2], hi + took[0::2]
+            flag = INF_CAPPED if (mg <= g).any() else 0
+            assert list(box[s]) == list(want_lo) + list(want_hi), (mg, s, box[s])
+            assert IR.same_bits(faces[6 * s:6 * s + 6], faces_of(CAV_ORIGIN, CAV_H, want_lo, want_hi)), (mg, s)
+            assert seg_flags[s] == flag and flags[s] == flag, (mg, s, seg_flags[s], flag)
+            G = int(g.max()) + 1
+            if mg >= G - 1:
+                assert list(box[s]) == list(a) + list(b) and (flag == 0) == (mg >= G), (mg, s)
+        assert np.array_equal(fo, 6 * np.arange(len(legs) + 1))
+
+
+def check_cavity_subdivide(be, a, b, legs):
+    """A leg whose seed lies in the cavity is clear: the batch comes back as it went in."""
+    v, so, W = cavity(a, b, legs)
+    T = 1.0 + 0.5 * np.arange(len(legs))
+    got = be.corridor_subdivide(so, W, CAV_ORIGIN, CAV_H, v, CAV_R, 4, T)
+    S = len(legs)
+    SR.assert_same(got, (so, W, T, np.arange(S, dtype=np.int32), np.zeros(S, np.int32), np.zeros(S, np.int32)), "cavity")
+
+
+# Placement: h = 2^-3, the origin and every waypoint on multiples of 2^-10.  Then every operation
+# of the seed is exact: mn - origin is a multiple of 2^-10 below 2^6, the quotient by h a multiple
+# of 2^-7, origin + h lo a multiple of 2^-10; and so are the points of the subdivision: w1 - w0 is
+# a multiple of 2^-10, (i / 16) times it one of 2^-14, the sum one of 2^-14.  Moving the origin by
+# -h offset while the map moves by +offset nodes in a larger grid changes every lattice index by
+# the offset and no plane, point or face.
+P_H, P_OFFSET, P_ORIGIN = 0.125, (3, 66, 5), (-2.5, -2.25, 0.25)
+
+
+def dyadic(lattice):
+    """Waypoints at the given lattice coordinates of the grid (P_ORIGIN, P_H), rounded to 2^-7 of a
+    cell, that is to multiples of 2^-10."""
+    W = np.array(P_ORIGIN) + P_H * (np.round(np.asarray(lattice, dtype=np.float64) * 128.0) / 128.0)
+    assert np.array_equal(W * 1024.0, np.round(W * 1024.0))
+    return W
+
+
+def embedded(values, pad=0.0):
+    """(values in a grid larger by P_OFFSET below and one layer above, the rest `pad` (not free);
+    the origin moved by -h offset)."""
+    nz, ny, nx = values.shape
+    ox, oy, oz = P_OFFSET
+    big = np.full((nz + oz + 1, ny + oy + 1, nx + ox + 1), pad, dtype=np.float32)
+    big[oz:oz + nz, oy:oy + ny, ox:ox + nx] = values
+    origin = tuple(float(o - P_H * d) for o, d in zip(P_ORIGIN, P_OFFSET))
+    assert all(o + P_H * d == p for o, d, p in zip(origin, P_OFFSET, P_ORIGIN))
+    return big, origin
+
+
+@functools.lru_cache(maxsize=None)
+def placed_scene():
+    """inflate_ref's scene and ragged batch at the same lattice coordinates of the dyadic grid."""
+    so, W = IR.ragged()
+    W = dyadic((W - np.array(IR.SCENE_ORIGIN)) / IR.SCENE_H)
+    W.setflags(write=False)
+    return so, W, IR.scene()
+
+
+def check_inflate_placement(be, max_grow=8, pad=0.0):
+    so, W, v = placed_scene()
+    base = be.corridor_inflate(so, W, P_ORIGIN, P_H, v, IR.SCENE_R, max_grow)
+    sf = base[3]
+    assert (sf & ~(INF_BLOCKED | INF_CAPPED) == 0).all()  # every seed is inside the original grid
+    blocked, grown = int((sf & INF_BLOCKED != 0).sum()), int((sf & INF_BLOCKED == 0).sum())
+    assert blocked >= len(sf) // 10 and grown >= len(sf) // 10, (blocked, grown, len(sf))
+    big, origin = embedded(v, pad)
+    moved = be.corridor_inflate(so, W, origin, P_H, big, IR.SCENE_R, max_grow)
+    shifted = (base[0] + np.array(P_OFFSET * 2, dtype=np.int32),) + tuple(base[1:])
+    IR.assert_same(moved, shifted)
+    return base
+
+
+@functools.lru_cache(maxsize=None)
+def placed_nodes():
+    """subdivide_ref's 17^3 map of 60 random nodes and its ragged batch on the dyadic grid."""
+    so, W, T = SR.ragged_in_grid(24, seed=5)
+    W = dyadic(W)  # G_ORIGIN = 0 and G_H = 1 there: the waypoints are lattice coordinates
+    v = SR.g_values(SR.random_nodes(60), bad=0.25)
+    for x in (W, T, v):
+        x.setflags(write=False)
+    return so, W, T, v
+
+
+def check_subdivide_placement(be, pad=0.0):
+    so, W, T, v = placed_nodes()
+    base = be.corridor_subdivide(so, W, P_ORIGIN, P_H, v, 0.3, 4, T)
+    flags, seg_flags = base[5], base[4]
+    assert (flags & SUB_DONE != 0).sum() >= len(flags) // 10 and (seg_flags & SUB_BLOCKED).any() and (seg_flags == 0).any()
+    big, origin = embedded(v, pad)
+    SR.assert_same(be.corridor_subdivide(so, W, origin, P_H, big, 0.3, 4, T), base, "placement")
+    return base
+
+
+def reversed_batch(so, W, T):
+    """Every trajectory flown backwards: its waypoint rows and its times in reverse order."""
+    W2, T2 = W.copy(), T.copy()
+    for b in range(len(so) - 1):
+        r0, r1 = int(so[b]) + b, int(so[b + 1]) + b + 1
+        W2[r0:r1] = W[r0:r1][::-1]
+        T2[so[b]:so[b + 1]] = T[so[b]:so[b + 1]][::-1]
+    return W2, T2
+
+
+def mirrored(so_in, out):
+    """The output of the subdivision as the reversed flight would report it."""
+    so2, W2, T2, parent, seg_flags, flags = out
+    W3, T3, par3, sf3 = W2.copy(), T2.copy(), parent.copy(), seg_flags.copy()
+    for b in range(len(so2) - 1):
+        s0, s1 = int(so2[b]), int(so2[b + 1])
+        W3[s0 + b:s1 + b + 1] = W2[s0 + b:s1 + b + 1][::-1]
+        T3[s0:s1], sf3[s0:s1] = T2[s0:s1][::-1], seg_flags[s0:s1][::-1]
+        par3[s0:s1] = (int(so_in[b]) + int(so_in[b + 1]) - 1 - parent[s0:s1])[::-1]
+    return so2, W3, T3, par3, sf3, flags
+
+
+def check_subdivide_reversal(be):
+    """On the dyadic grid P(i) of the leg w0 -> w1 and P(16 - i) of w1 -> w0 are the same double:
+    with w0, w1 multiples of 2^-10 below 2^5, w1 - w0 is exact, (i / 16)(w1 - w0) is a multiple of
+    2^-14 and exact, and so is the sum; both orders compute the same real number without rounding.
+    The seed takes the lesser and the greater of two points, so piece (k, j) of the reversed leg is
+    clear exactly when piece (k, 2^k - 1 - j) is, need() and the depth are the same, and the leaves
+    are the mirror image: rows, times, parents and leaf flags reversed, the flags equal."""
+    so, W, T, v = placed_nodes()
+    base = be.corridor_subdivide(so, W, P_ORIGIN, P_H, v, 0.3, 4, T)
+    Wr, Tr = reversed_batch(so, W, T)
+    back = be.corridor_subdivide(so, Wr, P_ORIGIN, P_H, v, 0.3, 4, Tr)
+    SR.assert_same(mirrored(so, back), base, "reversal")
+    assert not SR.same_bits(back[1], base[1])

@@ -1,0 +1,190 @@
+"""GPU: the map calls on the constructed maps of map_zoo.py, through the host-pointer calls on a
+GPU handle and through the device entry points (tgms_field_edt_device, tgms_field_occupancy_device,
+tgms_corridor_inflate_batch_device, tgms_corridor_subdivide_batch_device).
+test_map_zoo_host.py holds the closed forms against brute force and runs the same checks on the
+host backend; here the kernels' own launch paths are what is under test:
+    k_edt_rows   more than two trips of the grid-stride loop, the wavefront's LDS slices reused in
+                 each; the 256 chunks of the longest row, the carries crossing 255 empty ones
+    k_edt_lines  windows that start inside the line and span two or three stages, the last one short
+    k_occ_rows   nx at 63, 64, 65 and 128; more than two trips
+    k_occ_lines  line lengths around the unroll of 8
+and each call against itself: axis orders and reflections, embedding, placement, reversal.
+Every device output is pre-filled: NaN values, a d2 no call can produce, -3 in the workspace, -7 in
+the table, -2 and -9 in the rows, so a row or node a launch skipped is visible."""
+import numpy as np
+import pytest
+
+import edt_ref as ER
+import inflate_ref as IR
+import map_zoo as MZ
+from test_gpu_inflate import Device as InflateDevice
+from test_gpu_subdivide import run_device
+
+pytestmark = pytest.mark.gpu
+D2_SENTINEL = int(np.iinfo(np.int32).min)  # below -R^2 for every R
+
+
+def _dev(x):
+    import torch
+    return torch.from_numpy(np.array(x)).cuda()  # a copy: the shared inputs are read-only
+
+
+class Device(InflateDevice):
+    """The device entry points behind the backend interface of map_zoo.py: occupancy and
+    corridor_inflate as test_gpu_inflate.py wraps them, corridor_subdivide between the sentinel
+    rows of test_gpu_subdivide.py, field_edt as test_gpu_edt.py does with d2 pre-filled as well."""
+
+    def field_edt(self, occ, origin, h, max_dist, signed=False):
+        import torch
+        o = np.ascontiguousarray(occ, dtype=np.uint8)
+        n = o.shape[::-1]
+        nbytes = self.s.field_edt_work_size(origin, h, n, signed)
+        assert nbytes == 8 * o.size
+        work = torch.full((nbytes // 4,), -3, dtype=torch.int32, device="cuda")
+        v = torch.full(o.shape, float("nan"), dtype=torch.float32, device="cuda")
+        d2 = torch.full(o.shape, D2_SENTINEL, dtype=torch.int32, device="cuda")
+        self.s.field_edt_device(origin, h, n, _dev(o), max_dist, work, v, d2, signed)
+        torch.cuda.synchronize()
+        return v.cpu().numpy(), d2.cpu().numpy()
+
+    def corridor_subdivide(self, so, W, origin, h, values, r_free, max_depth, seg_times=None):
+        return run_device(self.s, so, W, seg_times, origin, h, values, r_free, max_depth)
+
+
+@pytest.fixture(scope="module", params=["host_pointers", "device"])
+def be(request, solver):
+    return solver if request.param == "host_pointers" else Device(solver)
+
+
+@pytest.fixture(scope="module")
+def host():
+    from trajectory_generator_ros2_amd.solver import Solver
+    with Solver(host=True) as s:
+        yield s
+
+
+FORMULA_IDS = [c[0] for c in MZ.FORMULA_CASES]
+CAVITY_IDS = [c[0] for c in MZ.CAVITIES]
+
+
+# ---- A. closed forms ----
+
+@pytest.mark.parametrize("case", MZ.FORMULA_CASES, ids=FORMULA_IDS)
+def test_closed_form_maps(be, case):
+    label, n, build = case
+    MZ.check_map(be, build(n), what=label)
+
+
+# ---- B. launch seams of the transform ----
+
+@pytest.mark.parametrize("name", ["two nodes", "last row"])
+def test_rows_beyond_two_trips(be, name):
+    """16,471 rows: every wavefront of the first 87 rows takes three trips, the others two, and the
+    last workgroup of the third trip has one row for its four wavefronts.  A row that no trip
+    reaches keeps the workspace's -3, and the line passes carry -3 + d^2 into every node around it;
+    a trip that reads the chunk masks of the row before finds a node in a row that has none."""
+    MZ.check_map(be, MZ.stride_map(name), what=name)
+
+
+@pytest.mark.parametrize("inverted", [False, True], ids=["node", "all but the node"])
+@pytest.mark.parametrize("name", list(MZ.LONG_TARGETS))
+def test_longest_row(be, name, inverted):
+    """nx = 16,384: chunk slots 0..255 of the wavefront's slices.  A node at i = 0 is carried
+    forward through 255 chunks without one (`last`), one at i = 16,383 backward (`s_next`); a
+    carry lost at a chunk gives FAR^2-sized squares capped to K from there on, a slot past 255
+    another wavefront's mask.  Three of the four rows have no node of their own: their squares come
+    from the line passes alone."""
+    MZ.check_map(be, MZ.long_map(name, inverted), caps=(None,), what=(name, inverted))
+
+
+@pytest.mark.parametrize("case", MZ.WINDOW_CASES, ids=ER.case_id)
+def test_windows_of_17_to_65_nodes(be, case):
+    """check_window asserts from the tile of 32 and the stage of 64 that some tile's window starts
+    inside the line (d = s - jw starts from an s that is no multiple of 64) and has a short last
+    stage.  A stage whose rows beyond `staged` were folded, or a d that restarts at the stage,
+    gives squares that are too small by whole rows."""
+    MZ.check_window(be, *case)
+
+
+# ---- C. the transform against itself ----
+
+@pytest.mark.parametrize("R", MZ.C_CAPS)
+def test_axis_orders_and_reflections(be, R):
+    MZ.check_axis_orders(be, R)
+
+
+@pytest.mark.parametrize("R", MZ.C_CAPS)
+def test_embedding_in_free_space(be, R):
+    MZ.check_embedding(be, R)
+
+
+@pytest.mark.parametrize("R", MZ.C_CAPS)
+def test_one_more_node_lowers_exactly_the_nearer_nodes(be, R):
+    MZ.check_one_more_node(be, R)
+
+
+@pytest.mark.parametrize("name", ["random_0.05", "random_0.5", "random_0.001"])
+def test_modes_agree_and_values_follow_d2(be, name):
+    MZ.check_modes(be, name, 3.2)
+    MZ.check_modes(be, name, 11.0)
+
+
+def test_seam_maps_equal_the_host_backend(solver, host):
+    """Host pointers, device buffers and the host backend on the three seam families at once."""
+    for m, R in ((MZ.stride_map("two nodes"), 2), (MZ.long_map("row 3 only", True), None)):
+        n = m.occ.shape[::-1]
+        md = MZ.far(n, 0.094) if R is None else 1.5 * 0.094
+        for signed in (False, True):
+            want = host.field_edt(m.occ, ER.ORIGIN, 0.094, md, signed)
+            ER.assert_same(solver.field_edt(m.occ, ER.ORIGIN, 0.094, md, signed), want, ("host pointers", n, signed))
+            ER.assert_same(Device(solver).field_edt(m.occ, ER.ORIGIN, 0.094, md, signed), want, ("device", n, signed))
+
+
+# ---- D. the table (the device only: the host backend has none) ----
+
+@pytest.mark.parametrize("n", MZ.TABLE_SEAMS + MZ.TABLE_PERM_GRIDS + IR.TABLE_GRIDS[:1] + IR.TABLE_GRIDS[2:], ids=MZ.grid_id)
+def test_table_closed_forms(solver, n):
+    """Entry (i, j, k) = i j k on a map without a free node, a step function for one non-free node.
+    A table row no trip reaches keeps -7; a carry dropped at a chunk end restarts the products of
+    that row at 0; an unrolled line step that skips its tail leaves the x sums unsummed there."""
+    MZ.check_table_closed_forms(Device(solver).occupancy, n)
+
+
+@pytest.mark.parametrize("n", MZ.TABLE_SEAMS, ids=MZ.grid_id)
+def test_table_seams_equal_cumsum(solver, n):
+    IR.check_table(Device(solver).occupancy, n)
+
+
+@pytest.mark.parametrize("n", MZ.TABLE_PERM_GRIDS, ids=MZ.grid_id)
+def test_table_axis_orders(solver, n):
+    MZ.check_table_axis_orders(Device(solver).occupancy, n)
+
+
+# ---- E. inflation and subdivision ----
+
+@pytest.mark.parametrize("case", MZ.CAVITIES, ids=CAVITY_IDS)
+def test_cavity_box_and_round_count(be, case):
+    MZ.check_cavity(be, *case[1:])
+
+
+@pytest.mark.parametrize("case", MZ.CAVITIES, ids=CAVITY_IDS)
+def test_cavity_legs_are_not_subdivided(be, case):
+    MZ.check_cavity_subdivide(be, *case[1:])
+
+
+@pytest.mark.parametrize("pad", [0.0, np.nan], ids=["pad 0", "pad NaN"])
+def test_inflation_ignores_the_placement(be, host, pad):
+    IR.assert_same(MZ.check_inflate_placement(be, pad=pad), MZ.check_inflate_placement(host, pad=pad))
+
+
+def test_inflation_ignores_the_placement_when_capped(be, host):
+    IR.assert_same(MZ.check_inflate_placement(be, max_grow=2), MZ.check_inflate_placement(host, max_grow=2))
+
+
+def test_subdivision_ignores_the_placement(be, host):
+    MZ.SR.assert_same(MZ.check_subdivide_placement(be), MZ.check_subdivide_placement(host), "against the host backend")
+    MZ.check_subdivide_placement(be, pad=np.nan)
+
+
+def test_subdivision_of_the_reversed_flight_is_the_mirror_image(be):
+    MZ.check_subdivide_reversal(be)

@@ -1,0 +1,137 @@
+"""CPU: the map calls that have a host backend (tgms_field_edt, tgms_corridor_inflate_batch and
+tgms_corridor_subdivide_batch on a tgms_create_host handle: csrc/tgms_edt_core.h,
+tgms_inflate_core.h, tgms_subdivide_core.h) on the constructed maps of map_zoo.py.  First the
+closed forms themselves are held against the brute force of edt_ref.py on grids of at most 20^3,
+and the placement and reversal relations against the NumPy references alone; then the host backend
+runs every check, the seam maps of the device kernels included (the formulas must hold there
+before they are asked of a kernel).  test_gpu_map_zoo.py runs the same checks through the GPU
+entry points and adds the table."""
+import numpy as np
+import pytest
+
+import edt_ref as ER
+import map_zoo as MZ
+
+
+@pytest.fixture(scope="module")
+def host():
+    from trajectory_generator_ros2_amd.solver import Solver
+    with Solver(host=True) as s:
+        yield s
+
+
+FORMULA_IDS = [c[0] for c in MZ.FORMULA_CASES]
+
+
+# ---- A. closed forms ----
+
+@pytest.mark.parametrize("case", MZ.FORMULA_CASES, ids=FORMULA_IDS)
+def test_closed_form_equals_brute_force(case):
+    _, n, build = case
+    MZ.check_formula(build(n))
+
+
+@pytest.mark.parametrize("case", MZ.FORMULA_CASES, ids=FORMULA_IDS)
+def test_closed_form_maps(host, case):
+    label, n, build = case
+    MZ.check_map(host, build(n), what=label)
+
+
+def test_closed_forms_of_the_seam_maps_on_a_small_grid():
+    """The builders of the large maps, with the same kind of placement, where brute force reaches."""
+    n = (20, 3, 2)
+    for q in ((0, 0, 0), (19, 0, 0), (11, 1, 1)):
+        m = MZ.nodes(n, [q])
+        MZ.check_formula(m)
+        MZ.check_formula(MZ.complement(m))
+    MZ.check_formula(MZ.nodes((3, 9, 20), [(1, 4, 2), (2, 5, 19)]))
+    MZ.check_formula(MZ.nodes((3, 9, 20), [(0, 8, 19)]))
+
+
+# ---- B. the seam maps of the device kernels, on the host backend ----
+
+@pytest.mark.parametrize("name", ["two nodes", "last row"])
+def test_rows_beyond_two_trips(host, name):
+    MZ.check_map(host, MZ.stride_map(name), what=name)
+
+
+@pytest.mark.parametrize("inverted", [False, True], ids=["node", "all but the node"])
+@pytest.mark.parametrize("name", list(MZ.LONG_TARGETS))
+def test_longest_row(host, name, inverted):
+    MZ.check_map(host, MZ.long_map(name, inverted), caps=(None,), what=(name, inverted))
+
+
+@pytest.mark.parametrize("case", MZ.WINDOW_CASES, ids=ER.case_id)
+def test_windows_of_17_to_65_nodes(host, case):
+    MZ.check_window(host, *case)
+
+
+def test_window_seam_is_what_the_cases_need():
+    """A window that starts inside the line and spans several stages needs R >= 17 on 130 nodes; the
+    caps the matrix of edt_ref.py uses do not have it."""
+    assert MZ.window_seam(130, 16) == (False, False) and MZ.window_seam(130, 2)[0] is False
+    assert MZ.window_seam(64, 11)[0] is False and MZ.window_seam(130, 1 << 15)[0] is False
+    for R in MZ.WINDOW_R:
+        assert MZ.window_seam(130, R) == (True, True), R
+
+
+# ---- C. the transform against itself ----
+
+@pytest.mark.parametrize("R", MZ.C_CAPS)
+def test_axis_orders_and_reflections(host, R):
+    MZ.check_axis_orders(host, R)
+
+
+@pytest.mark.parametrize("R", MZ.C_CAPS)
+def test_embedding_in_free_space(host, R):
+    MZ.check_embedding(host, R)
+
+
+@pytest.mark.parametrize("R", MZ.C_CAPS)
+def test_one_more_node_lowers_exactly_the_nearer_nodes(host, R):
+    MZ.check_one_more_node(host, R)
+
+
+@pytest.mark.parametrize("name", ["random_0.05", "random_0.5", "random_0.001"])
+def test_modes_agree_and_values_follow_d2(host, name):
+    MZ.check_modes(host, name, 3.2)
+    MZ.check_modes(host, name, 11.0)
+
+
+# ---- E. inflation and subdivision ----
+
+CAVITY_IDS = [c[0] for c in MZ.CAVITIES]
+
+
+@pytest.mark.parametrize("case", MZ.CAVITIES, ids=CAVITY_IDS)
+def test_cavity_box_and_round_count(host, case):
+    MZ.check_cavity(MZ.Reference(), *case[1:])
+    MZ.check_cavity(host, *case[1:])
+
+
+@pytest.mark.parametrize("case", MZ.CAVITIES, ids=CAVITY_IDS)
+def test_cavity_legs_are_not_subdivided(host, case):
+    MZ.check_cavity_subdivide(MZ.Reference(), *case[1:])
+    MZ.check_cavity_subdivide(host, *case[1:])
+
+
+@pytest.mark.parametrize("pad", [0.0, np.nan], ids=["pad 0", "pad NaN"])
+def test_inflation_ignores_the_placement(host, pad):
+    ref = MZ.check_inflate_placement(MZ.Reference(), pad=pad)
+    MZ.IR.assert_same(MZ.check_inflate_placement(host, pad=pad), ref)
+
+
+def test_inflation_ignores_the_placement_when_capped(host):
+    ref = MZ.check_inflate_placement(MZ.Reference(), max_grow=2)
+    MZ.IR.assert_same(MZ.check_inflate_placement(host, max_grow=2), ref)
+
+
+def test_subdivision_ignores_the_placement(host):
+    ref = MZ.check_subdivide_placement(MZ.Reference())
+    MZ.SR.assert_same(MZ.check_subdivide_placement(host), ref, "host")
+    MZ.check_subdivide_placement(host, pad=np.nan)
+
+
+def test_subdivision_of_the_reversed_flight_is_the_mirror_image(host):
+    MZ.check_subdivide_reversal(MZ.Reference())
+    MZ.check_subdivide_reversal(host)
