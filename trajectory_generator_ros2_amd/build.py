@@ -29,7 +29,8 @@ HIP_SOURCES = ["tgms_reduced.hip", "tgms_dense.hip", "tgms_band.hip", "tgms_samp
                "tgms_bounds.hip", "tgms_thrust.hip", "tgms_rate.hip", "tgms_dilate.hip", "tgms_corridor.hip",
                "tgms_corridor_split.hip", "tgms_cut.hip", "tgms_separation.hip", "tgms_neighbors.hip",
                "tgms_clearance.hip", "tgms_field.hip", "tgms_inflate.hip", "tgms_subdivide.hip",
-               "tgms_edt.hip", "tgms_capi.hip"]
+               "tgms_edt.hip", "tgms_capi.hip", "tgms_capi_multi.hip",
+               "tgms_capi_analysis.hip", "tgms_capi_map.hip"]
 CXX_SOURCES = ["tgms_plan.cpp", "tgms_host.cpp"]  # host-only (no HIP): compiled by g++ into the same library
 HOST_SOURCES = ["MinSnap.cpp", "factory.cpp", "tgms_node_capi.cpp"]
 
@@ -66,7 +67,7 @@ def build_tgms(force: bool = False) -> str:
     cobjs = [os.path.join(OBJDIR, os.path.basename(s) + ".o") for s in csrcs]
     ctodo = [(s, o) for s, o in zip(csrcs, cobjs) if force or _newer(o, [s] + hdrs)]
     cxx = ["g++", "-O2", "-std=c++17", "-fPIC", "-Wall", "-Wextra", "-I" + INCLUDE, "-I" + CSRC]
-    with ThreadPoolExecutor(max_workers=len(srcs) + len(csrcs)) as ex:
+    with ThreadPoolExecutor(max_workers=min(16, len(srcs) + len(csrcs))) as ex:
         jobs = [ex.submit(_run, [HIPCC] + HIP_FLAGS + ["-c", s, "-o", o]) for s, o in todo]
         jobs += [ex.submit(_run, cxx + ["-c", s, "-o", o]) for s, o in ctodo]
         for j in jobs:

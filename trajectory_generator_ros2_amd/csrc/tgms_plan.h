@@ -3,7 +3,7 @@
 // Pure C++ (no HIP, no RCCL): the shard cuts, the pieces of every shard, the byte layout
 // of every device's piece workspace and the complete list of point-to-point transfers
 // (scatter of the inputs from device 0, gather of the results back to device 0) are
-// computed here, and tgms_capi.hip's multi_enqueue only turns that list into grouped
+// computed here, and tgms_capi_multi.hip's multi_enqueue only turns that list into grouped
 // ncclSend / ncclRecv calls (rccl.h:700/722) and kernel launches.  The same code is
 // exported through tgms_multi_schedule (include/tgms.h), so the schedule is checked on
 // the CPU at 2..8 devices (tests/test_multi_schedule.py) without a GPU or RCCL.

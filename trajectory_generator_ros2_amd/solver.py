@@ -27,6 +27,16 @@ def _ptr(a) -> Optional[int]:
     return a.data_ptr()
 
 
+def _csr(seg_offsets, waypoints=None, seg_times=None, coeffs=None, end_derivs=None):
+    """The CSR inputs as the C ABI takes them, None staying None: (seg_offsets int32, waypoints
+    [-1,3], seg_times [-1], coeffs (shape kept), end_derivs [-1,18]), the last four float64."""
+    def f64(a, *shape):
+        a = None if a is None else np.ascontiguousarray(a, dtype=np.float64)
+        return a if a is None or not shape else a.reshape(*shape)
+    return (np.ascontiguousarray(seg_offsets, dtype=np.int32), f64(waypoints, -1, 3), f64(seg_times, -1), f64(coeffs),
+            f64(end_derivs, -1, 18))
+
+
 class Solver:
     """A libtgms handle bound to one HIP device (or, asked for explicitly, the host backend)."""
 
@@ -73,10 +83,12 @@ class Solver:
     def last_error(self) -> str:
         return self._L.tgms_last_error(self._h).decode()
 
-    def set_method(self, method: int):
-        st = self._L.tgms_set_method(self._h, int(method))
+    def _check(self, st: int) -> None:
         if st != _lib.OK:
             raise TgmsError(st, self.last_error())
+
+    def set_method(self, method: int):
+        self._check(self._L.tgms_set_method(self._h, int(method)))
         self.method = method
 
     # ---------------------------------------------------------------- host API
@@ -86,10 +98,7 @@ class Solver:
 
         `out` = (coeffs, status) reuses caller buffers (float64 [S,3,8], int32 [>=B]):
         fresh host pages fault in during the device-to-host copy, reused ones do not."""
-        so = np.ascontiguousarray(seg_offsets, dtype=np.int32)
-        W = np.ascontiguousarray(waypoints, dtype=np.float64).reshape(-1, 3)
-        T = np.ascontiguousarray(seg_times, dtype=np.float64).reshape(-1)
-        ED = None if end_derivs is None else np.ascontiguousarray(end_derivs, dtype=np.float64).reshape(-1, 18)
+        so, W, T, _, ED = _csr(seg_offsets, waypoints, seg_times, end_derivs=end_derivs)
         B = so.shape[0] - 1
         S = int(so[-1]) if B > 0 else 0
         if out is not None:
@@ -108,10 +117,7 @@ class Solver:
 
     def solve_multi(self, seg_offsets, waypoints, seg_times, end_derivs=None) -> Tuple[np.ndarray, np.ndarray, int]:
         """tgms_solve_batch_multi: host batch over every device of the handle."""
-        so = np.ascontiguousarray(seg_offsets, dtype=np.int32)
-        W = np.ascontiguousarray(waypoints, dtype=np.float64).reshape(-1, 3)
-        T = np.ascontiguousarray(seg_times, dtype=np.float64).reshape(-1)
-        ED = None if end_derivs is None else np.ascontiguousarray(end_derivs, dtype=np.float64).reshape(-1, 18)
+        so, W, T, _, ED = _csr(seg_offsets, waypoints, seg_times, end_derivs=end_derivs)
         B = so.shape[0] - 1
         C = np.zeros((int(so[-1]) if B > 0 else 0, 3, 8), dtype=np.float64)
         st = np.zeros(max(B, 1), dtype=np.int32)
@@ -122,18 +128,13 @@ class Solver:
 
     def sample(self, seg_offsets, waypoints, seg_times, end_derivs, coeffs, dt: float,
                yaw_mode: int = _lib.YAW_CONSTANT, yaw_const: float = 0.0):
-        so = np.ascontiguousarray(seg_offsets, dtype=np.int32)
-        W = np.ascontiguousarray(waypoints, dtype=np.float64).reshape(-1, 3)
-        T = np.ascontiguousarray(seg_times, dtype=np.float64).reshape(-1)
-        ED = None if end_derivs is None else np.ascontiguousarray(end_derivs, dtype=np.float64).reshape(-1, 18)
-        C = np.ascontiguousarray(coeffs, dtype=np.float64)
+        so, W, T, C, ED = _csr(seg_offsets, waypoints, seg_times, coeffs, end_derivs)
         B = so.shape[0] - 1
         offs = sample_offsets(so, T, dt)
         out = np.zeros((int(offs[-1]), _lib.GOAL_STRIDE), dtype=np.float64)
-        st = self._L.tgms_sample_batch(self._h, B, _ptr(so), _ptr(W), _ptr(T), _ptr(ED), _ptr(C), float(dt),
-                                       int(yaw_mode), float(yaw_const), _ptr(offs), _ptr(out))
-        if st != _lib.OK:
-            raise TgmsError(st, self.last_error())
+        self._check(self._L.tgms_sample_batch(
+            self._h, B, _ptr(so), _ptr(W), _ptr(T), _ptr(ED), _ptr(C), float(dt), int(yaw_mode), float(yaw_const),
+            _ptr(offs), _ptr(out)))
         return offs, out
 
     def extrema(self, seg_offsets, waypoints, seg_times, end_derivs, coeffs, dt: float,
@@ -141,18 +142,13 @@ class Solver:
         """Feasibility check at dt (include/tgms.h tgms_extrema_batch): (extrema [B,10] =
         pmin pmax v_peak a_peak j_peak duration, flags [B] of FEAS_* bits against `limits`;
         None checks nothing, so only FEAS_NONFINITE can appear)."""
-        so = np.ascontiguousarray(seg_offsets, dtype=np.int32)
-        W = np.ascontiguousarray(waypoints, dtype=np.float64).reshape(-1, 3)
-        T = np.ascontiguousarray(seg_times, dtype=np.float64).reshape(-1)
-        ED = None if end_derivs is None else np.ascontiguousarray(end_derivs, dtype=np.float64).reshape(-1, 18)
-        C = np.ascontiguousarray(coeffs, dtype=np.float64)
+        so, W, T, C, ED = _csr(seg_offsets, waypoints, seg_times, coeffs, end_derivs)
         B = so.shape[0] - 1
         ext = np.zeros((B, _lib.EXTREMA_STRIDE), dtype=np.float64)
         flags = np.zeros(B, dtype=np.int32)
-        st = self._L.tgms_extrema_batch(self._h, B, _ptr(so), _ptr(W), _ptr(T), _ptr(ED), _ptr(C), float(dt),
-                                        None if limits is None else ctypes.byref(limits), _ptr(ext), _ptr(flags))
-        if st != _lib.OK:
-            raise TgmsError(st, self.last_error())
+        self._check(self._L.tgms_extrema_batch(
+            self._h, B, _ptr(so), _ptr(W), _ptr(T), _ptr(ED), _ptr(C), float(dt),
+            None if limits is None else ctypes.byref(limits), _ptr(ext), _ptr(flags)))
         return ext, flags
 
     def bounds(self, seg_offsets, seg_times, coeffs,
@@ -160,16 +156,13 @@ class Solver:
         """Continuous feasibility bounds (include/tgms.h tgms_bounds_batch): the record and
         flags of extrema(), from the polynomials' stationary points on every segment's closed
         interval instead of samples at a dt."""
-        so = np.ascontiguousarray(seg_offsets, dtype=np.int32)
-        T = np.ascontiguousarray(seg_times, dtype=np.float64).reshape(-1)
-        C = np.ascontiguousarray(coeffs, dtype=np.float64)
+        so, _, T, C, _ = _csr(seg_offsets, seg_times=seg_times, coeffs=coeffs)
         B = so.shape[0] - 1
         ext = np.zeros((B, _lib.EXTREMA_STRIDE), dtype=np.float64)
         flags = np.zeros(B, dtype=np.int32)
-        st = self._L.tgms_bounds_batch(self._h, B, _ptr(so), _ptr(T), _ptr(C),
-                                       None if limits is None else ctypes.byref(limits), _ptr(ext), _ptr(flags))
-        if st != _lib.OK:
-            raise TgmsError(st, self.last_error())
+        self._check(self._L.tgms_bounds_batch(
+            self._h, B, _ptr(so), _ptr(T), _ptr(C), None if limits is None else ctypes.byref(limits), _ptr(ext),
+            _ptr(flags)))
         return ext, flags
 
     def thrust(self, seg_offsets, seg_times, coeffs, g: float = 9.80665,
@@ -177,16 +170,13 @@ class Solver:
         """Continuous thrust and tilt bounds (include/tgms.h tgms_thrust_batch): (rec [B,6] =
         f_min t_fmin f_max t_fmax tilt_max t_tilt of the mass-normalised thrust p'' + g e_z,
         flags [B] of THRUST_* bits against `limits`; None checks nothing)."""
-        so = np.ascontiguousarray(seg_offsets, dtype=np.int32)
-        T = np.ascontiguousarray(seg_times, dtype=np.float64).reshape(-1)
-        C = np.ascontiguousarray(coeffs, dtype=np.float64)
+        so, _, T, C, _ = _csr(seg_offsets, seg_times=seg_times, coeffs=coeffs)
         B = so.shape[0] - 1
         rec = np.zeros((B, _lib.THRUST_STRIDE), dtype=np.float64)
         flags = np.zeros(B, dtype=np.int32)
-        st = self._L.tgms_thrust_batch(self._h, B, _ptr(so), _ptr(T), _ptr(C), float(g),
-                                       None if limits is None else ctypes.byref(limits), _ptr(rec), _ptr(flags))
-        if st != _lib.OK:
-            raise TgmsError(st, self.last_error())
+        self._check(self._L.tgms_thrust_batch(
+            self._h, B, _ptr(so), _ptr(T), _ptr(C), float(g), None if limits is None else ctypes.byref(limits),
+            _ptr(rec), _ptr(flags)))
         return rec, flags
 
     def rate(self, seg_offsets, seg_times, coeffs, g: float = 9.80665,
@@ -195,17 +185,14 @@ class Solver:
         t_omega of the roll/pitch rate ||f x p'''|| / ||f||^2 with f = p'' + g e_z, seg_rec [S,2]
         = each segment's own maximum and local time, flags [B]: RATE_HIGH against `omega_limit`;
         inf checks nothing)."""
-        so = np.ascontiguousarray(seg_offsets, dtype=np.int32)
-        T = np.ascontiguousarray(seg_times, dtype=np.float64).reshape(-1)
-        C = np.ascontiguousarray(coeffs, dtype=np.float64)
+        so, _, T, C, _ = _csr(seg_offsets, seg_times=seg_times, coeffs=coeffs)
         B = so.shape[0] - 1
         rec = np.zeros((B, _lib.RATE_STRIDE), dtype=np.float64)
         seg_rec = np.zeros((T.shape[0], _lib.RATE_STRIDE), dtype=np.float64)
         flags = np.zeros(B, dtype=np.int32)
-        st = self._L.tgms_rate_batch(self._h, B, _ptr(so), _ptr(T), _ptr(C), float(g), float(omega_limit),
-                                     _ptr(rec), _ptr(seg_rec), _ptr(flags))
-        if st != _lib.OK:
-            raise TgmsError(st, self.last_error())
+        self._check(self._L.tgms_rate_batch(
+            self._h, B, _ptr(so), _ptr(T), _ptr(C), float(g), float(omega_limit), _ptr(rec), _ptr(seg_rec),
+            _ptr(flags)))
         return rec, seg_rec, flags
 
     def dilate(self, seg_offsets, seg_times, coeffs, g: float = 9.80665, limits: Optional[_lib.Limits] = None,
@@ -215,20 +202,16 @@ class Solver:
         `tlimits` (None: unchecked).  Returns (scale [B], active [B] of DIL_* codes, flags [B] =
         DIL_CAPPED / FEAS_NONFINITE with the evaluation count above DIL_EVALS_SHIFT, seg_times_out
         [S] = s T, coeffs_out [S,3,8] = c_k / s^k)."""
-        so = np.ascontiguousarray(seg_offsets, dtype=np.int32)
-        T = np.ascontiguousarray(seg_times, dtype=np.float64).reshape(-1)
-        C = np.ascontiguousarray(coeffs, dtype=np.float64)
+        so, _, T, C, _ = _csr(seg_offsets, seg_times=seg_times, coeffs=coeffs)
         B = so.shape[0] - 1
         scale = np.zeros(B, dtype=np.float64)
         active = np.zeros(B, dtype=np.int32)
         flags = np.zeros(B, dtype=np.int32)
         T_out, C_out = np.zeros_like(T), np.zeros_like(C)
-        st = self._L.tgms_dilate_batch(self._h, B, _ptr(so), _ptr(T), _ptr(C), float(g),
-                                       None if limits is None else ctypes.byref(limits),
-                                       None if tlimits is None else ctypes.byref(tlimits), float(s_lo), float(s_hi),
-                                       _ptr(scale), _ptr(active), _ptr(flags), _ptr(T_out), _ptr(C_out))
-        if st != _lib.OK:
-            raise TgmsError(st, self.last_error())
+        self._check(self._L.tgms_dilate_batch(
+            self._h, B, _ptr(so), _ptr(T), _ptr(C), float(g), None if limits is None else ctypes.byref(limits),
+            None if tlimits is None else ctypes.byref(tlimits), float(s_lo), float(s_hi), _ptr(scale), _ptr(active),
+            _ptr(flags), _ptr(T_out), _ptr(C_out)))
         return scale, active, flags, T_out, C_out
 
     def corridor(self, seg_offsets, seg_times, coeffs, faces, face_offsets=None, r: float = 0.0):
@@ -237,9 +220,7 @@ class Solver:
         applies all F (at most COR_MAX_FACES) to every segment.  Returns (rec [B,2] = m_max
         t_max, where [B,2] = segment, face, seg_rec [S,2] = m_s t_s, seg_face [S], flags [B] of
         COR_* bits; COR_OUTSIDE when m_max > -r)."""
-        so = np.ascontiguousarray(seg_offsets, dtype=np.int32)
-        T = np.ascontiguousarray(seg_times, dtype=np.float64).reshape(-1)
-        C = np.ascontiguousarray(coeffs, dtype=np.float64)
+        so, _, T, C, _ = _csr(seg_offsets, seg_times=seg_times, coeffs=coeffs)
         fc = np.ascontiguousarray(faces, dtype=np.float64).reshape(-1, 4)
         fo = None if face_offsets is None else np.ascontiguousarray(face_offsets, dtype=np.int64)
         B, S = so.shape[0] - 1, int(so[-1])
@@ -248,11 +229,9 @@ class Solver:
         seg_rec = np.zeros((S, _lib.COR_STRIDE), dtype=np.float64)
         seg_face = np.zeros(S, dtype=np.int32)
         flags = np.zeros(B, dtype=np.int32)
-        st = self._L.tgms_corridor_batch(self._h, B, _ptr(so), _ptr(T), _ptr(C), fc.shape[0],
-                                         _ptr(fc) if fc.shape[0] else None, _ptr(fo), float(r), _ptr(rec),
-                                         _ptr(where), _ptr(seg_rec), _ptr(seg_face), _ptr(flags))
-        if st != _lib.OK:
-            raise TgmsError(st, self.last_error())
+        self._check(self._L.tgms_corridor_batch(
+            self._h, B, _ptr(so), _ptr(T), _ptr(C), fc.shape[0], _ptr(fc) if fc.shape[0] else None, _ptr(fo), float(r),
+            _ptr(rec), _ptr(where), _ptr(seg_rec), _ptr(seg_face), _ptr(flags)))
         return rec, where, seg_rec, seg_face, flags
 
     def corridor_split(self, seg_offsets, waypoints, seg_times, coeffs, faces, face_offsets, seg_rec, seg_face,
@@ -263,10 +242,7 @@ class Solver:
         F' faces: (seg_offsets' [B+1], waypoints' [S'+B,3], seg_times' [S'], faces' [F',4],
         face_offsets' [S'+1], parent [S'], flags [B] of SPLIT_* bits); in shared mode
         (face_offsets None) faces' is `faces` and face_offsets' is None."""
-        so = np.ascontiguousarray(seg_offsets, dtype=np.int32)
-        W = np.ascontiguousarray(waypoints, dtype=np.float64).reshape(-1, 3)
-        T = np.ascontiguousarray(seg_times, dtype=np.float64).reshape(-1)
-        C = np.ascontiguousarray(coeffs, dtype=np.float64)
+        so, W, T, C, _ = _csr(seg_offsets, waypoints, seg_times, coeffs)
         fc = np.ascontiguousarray(faces, dtype=np.float64).reshape(-1, 4)
         fo = None if face_offsets is None else np.ascontiguousarray(face_offsets, dtype=np.int64)
         sr = np.ascontiguousarray(seg_rec, dtype=np.float64).reshape(-1, _lib.COR_STRIDE)
@@ -280,13 +256,10 @@ class Solver:
         parent = np.zeros(2 * S, dtype=np.int32)
         totals = np.zeros(2, dtype=np.int64)
         flags = np.zeros(B, dtype=np.int32)
-        st = self._L.tgms_corridor_split_batch(self._h, B, _ptr(so), _ptr(W), _ptr(T), _ptr(C), F,
-                                               _ptr(fc) if F else None, _ptr(fo), _ptr(sr), _ptr(sf), float(r),
-                                               int(mode), float(min_frac), _ptr(so2), _ptr(W2), _ptr(T2),
-                                               _ptr(fc2) if fc2 is not None and F else None, _ptr(fo2), _ptr(parent),
-                                               _ptr(totals), _ptr(flags))
-        if st != _lib.OK:
-            raise TgmsError(st, self.last_error())
+        self._check(self._L.tgms_corridor_split_batch(
+            self._h, B, _ptr(so), _ptr(W), _ptr(T), _ptr(C), F, _ptr(fc) if F else None, _ptr(fo), _ptr(sr), _ptr(sf),
+            float(r), int(mode), float(min_frac), _ptr(so2), _ptr(W2), _ptr(T2),
+            _ptr(fc2) if fc2 is not None and F else None, _ptr(fo2), _ptr(parent), _ptr(totals), _ptr(flags)))
         S2, F2 = int(totals[0]), int(totals[1])
         if fo is None:
             return so2, W2[:S2 + B], T2[:S2], fc, None, parent[:S2], flags
@@ -298,12 +271,8 @@ class Solver:
         t_cut [B].  Returns the new batch trimmed to its S' segments: (seg_offsets' [B+1],
         waypoints' [S'+B,3], seg_times' [S'], end_derivs' [B,18], coeffs' [S',3,8] (the tail without
         a solve; None when want_coeffs is False), parent [S'], t0 [B], flags [B] of CUT_* bits)."""
-        so = np.ascontiguousarray(seg_offsets, dtype=np.int32)
-        W = np.ascontiguousarray(waypoints, dtype=np.float64).reshape(-1, 3)
-        T = np.ascontiguousarray(seg_times, dtype=np.float64).reshape(-1)
-        C = np.ascontiguousarray(coeffs, dtype=np.float64)
+        so, W, T, C, ED = _csr(seg_offsets, waypoints, seg_times, coeffs, end_derivs)
         tc = np.ascontiguousarray(t_cut, dtype=np.float64).reshape(-1)
-        ED = None if end_derivs is None else np.ascontiguousarray(end_derivs, dtype=np.float64).reshape(-1, 18)
         B = so.shape[0] - 1
         S = int(so[-1]) if B > 0 else 0
         if tc.shape[0] != B:
@@ -317,11 +286,9 @@ class Solver:
         t0 = np.zeros(B, dtype=np.float64)
         totals = np.zeros(1, dtype=np.int64)
         flags = np.zeros(B, dtype=np.int32)
-        st = self._L.tgms_cut_batch(self._h, B, _ptr(so), _ptr(W), _ptr(T), _ptr(ED), _ptr(C), _ptr(tc),
-                                    float(min_frac), _ptr(so2), _ptr(W2), _ptr(T2), _ptr(ED2), _ptr(C2), _ptr(parent),
-                                    _ptr(t0), _ptr(totals), _ptr(flags))
-        if st != _lib.OK:
-            raise TgmsError(st, self.last_error())
+        self._check(self._L.tgms_cut_batch(
+            self._h, B, _ptr(so), _ptr(W), _ptr(T), _ptr(ED), _ptr(C), _ptr(tc), float(min_frac), _ptr(so2), _ptr(W2),
+            _ptr(T2), _ptr(ED2), _ptr(C2), _ptr(parent), _ptr(t0), _ptr(totals), _ptr(flags)))
         S2 = int(totals[0])
         return so2, W2[:S2 + B], T2[:S2], ED2, None if C2 is None else C2[:S2], parent[:S2], t0, flags
 
@@ -335,8 +302,7 @@ class Solver:
         flagged = []
         while True:
             C, _, worst = self.solve(so, W, T, end_derivs)
-            if worst != _lib.OK:
-                raise TgmsError(worst, self.last_error())
+            self._check(worst)
             _, _, seg_rec, seg_face, fl = self.corridor(so, T, C, fc, fo, r)
             flagged.append(int(((fl & _lib.COR_OUTSIDE) != 0).sum()))
             if flagged[-1] == 0 or len(flagged) > rounds:
@@ -349,9 +315,7 @@ class Solver:
         closest approach (sep [P,2] = d_min t_min, flags [P] of SEP_* bits).  pairs: int32
         [P,2], or None for every unordered pair (0,1), (0,2), ..., (1,2), ...; start_times [B]
         (None: all 0); scale: the three per-axis factors (None: 1, 1, 1)."""
-        so = np.ascontiguousarray(seg_offsets, dtype=np.int32)
-        T = np.ascontiguousarray(seg_times, dtype=np.float64).reshape(-1)
-        C = np.ascontiguousarray(coeffs, dtype=np.float64)
+        so, _, T, C, _ = _csr(seg_offsets, seg_times=seg_times, coeffs=coeffs)
         t0 = None if start_times is None else np.ascontiguousarray(start_times, dtype=np.float64).reshape(-1)
         sc = None if scale is None else np.ascontiguousarray(scale, dtype=np.float64).reshape(3)
         B = so.shape[0] - 1
@@ -362,28 +326,24 @@ class Solver:
             P = pr.shape[0]
         sep = np.full((P, _lib.SEP_STRIDE), np.nan, dtype=np.float64)
         flags = np.full(P, -1, dtype=np.int32)
-        st = self._L.tgms_separation_batch(self._h, B, _ptr(so), _ptr(T), _ptr(C), _ptr(t0), P, _ptr(pr), _ptr(sc),
-                                           float(r_min), _ptr(sep), _ptr(flags))
-        if st != _lib.OK:
-            raise TgmsError(st, self.last_error())
+        self._check(self._L.tgms_separation_batch(
+            self._h, B, _ptr(so), _ptr(T), _ptr(C), _ptr(t0), P, _ptr(pr), _ptr(sc), float(r_min), _ptr(sep),
+            _ptr(flags)))
         return sep, flags
 
     def neighbors(self, seg_offsets, seg_times, coeffs, r_min: float, start_times=None, scale=None):
         """Swarm neighbour search (include/tgms.h tgms_neighbors_batch): per vehicle the nearest
         other vehicle whose closest approach is below r_min.  Returns (near [B,2] = d_min t_min,
         nbr [B] (NEAR_NONE: nobody), count [B], tested [B], flags [B] of SEP_* bits)."""
-        so = np.ascontiguousarray(seg_offsets, dtype=np.int32)
-        T = np.ascontiguousarray(seg_times, dtype=np.float64).reshape(-1)
-        C = np.ascontiguousarray(coeffs, dtype=np.float64)
+        so, _, T, C, _ = _csr(seg_offsets, seg_times=seg_times, coeffs=coeffs)
         t0 = None if start_times is None else np.ascontiguousarray(start_times, dtype=np.float64).reshape(-1)
         sc = None if scale is None else np.ascontiguousarray(scale, dtype=np.float64).reshape(3)
         B = so.shape[0] - 1
         near = np.full((B, _lib.SEP_STRIDE), np.nan, dtype=np.float64)
         nbr, count, tested, flags = (np.full(B, -2, dtype=np.int32) for _ in range(4))
-        st = self._L.tgms_neighbors_batch(self._h, B, _ptr(so), _ptr(T), _ptr(C), _ptr(t0), _ptr(sc), float(r_min),
-                                          _ptr(near), _ptr(nbr), _ptr(count), _ptr(tested), _ptr(flags))
-        if st != _lib.OK:
-            raise TgmsError(st, self.last_error())
+        self._check(self._L.tgms_neighbors_batch(
+            self._h, B, _ptr(so), _ptr(T), _ptr(C), _ptr(t0), _ptr(sc), float(r_min), _ptr(near), _ptr(nbr),
+            _ptr(count), _ptr(tested), _ptr(flags)))
         return near, nbr, count, tested, flags
 
     def clearance(self, seg_offsets, seg_times, coeffs, obstacles, r_min: float, scale=None):
@@ -391,18 +351,15 @@ class Solver:
         the static boxes `obstacles` [K,6] = lo[3] hi[3] whose distance falls below r_min.  Returns
         (near [B,2] = d_min t_min, obs [B] (NEAR_NONE: none), count [B], tested [B], flags [B] of
         SEP_* bits and CLR_BAD_OBSTACLE)."""
-        so = np.ascontiguousarray(seg_offsets, dtype=np.int32)
-        T = np.ascontiguousarray(seg_times, dtype=np.float64).reshape(-1)
-        C = np.ascontiguousarray(coeffs, dtype=np.float64)
+        so, _, T, C, _ = _csr(seg_offsets, seg_times=seg_times, coeffs=coeffs)
         ob = np.ascontiguousarray(obstacles, dtype=np.float64).reshape(-1, 6)
         sc = None if scale is None else np.ascontiguousarray(scale, dtype=np.float64).reshape(3)
         B, K = so.shape[0] - 1, ob.shape[0]
         near = np.full((B, _lib.SEP_STRIDE), np.nan, dtype=np.float64)
         obs, count, tested, flags = (np.full(B, -2, dtype=np.int32) for _ in range(4))
-        st = self._L.tgms_clearance_batch(self._h, B, _ptr(so), _ptr(T), _ptr(C), K, _ptr(ob) if K else None, _ptr(sc),
-                                          float(r_min), _ptr(near), _ptr(obs), _ptr(count), _ptr(tested), _ptr(flags))
-        if st != _lib.OK:
-            raise TgmsError(st, self.last_error())
+        self._check(self._L.tgms_clearance_batch(
+            self._h, B, _ptr(so), _ptr(T), _ptr(C), K, _ptr(ob) if K else None, _ptr(sc), float(r_min), _ptr(near),
+            _ptr(obs), _ptr(count), _ptr(tested), _ptr(flags)))
         return near, obs, count, tested, flags
 
     def field_clearance(self, seg_offsets, seg_times, coeffs, origin, h: float, values, r_min: float, tol: float,
@@ -412,20 +369,16 @@ class Solver:
         spacing h) along it, certified to tol below r_min.  lip: a Lipschitz bound of the field,
         0 to have it reduced from the values.  Returns (near [B,2] = d_min t_min, evals [B],
         flags [B] of SEP_* bits and FLD_UNRESOLVED)."""
-        so = np.ascontiguousarray(seg_offsets, dtype=np.int32)
-        T = np.ascontiguousarray(seg_times, dtype=np.float64).reshape(-1)
-        C = np.ascontiguousarray(coeffs, dtype=np.float64)
+        so, _, T, C, _ = _csr(seg_offsets, seg_times=seg_times, coeffs=coeffs)
         v = np.ascontiguousarray(values, dtype=np.float32)
         assert v.ndim == 3, "values must be [nz, ny, nx]"
         fld = _lib.Field(origin, h, v.shape[::-1])
         B = so.shape[0] - 1
         near = np.full((B, _lib.SEP_STRIDE), np.nan, dtype=np.float64)
         evals, flags = (np.full(B, -2, dtype=np.int32) for _ in range(2))
-        st = self._L.tgms_field_clearance_batch(self._h, B, _ptr(so), _ptr(T), _ptr(C), ctypes.byref(fld), _ptr(v),
-                                                float(lip), float(r_min), float(tol), int(max_evals), _ptr(near),
-                                                _ptr(evals), _ptr(flags))
-        if st != _lib.OK:
-            raise TgmsError(st, self.last_error())
+        self._check(self._L.tgms_field_clearance_batch(
+            self._h, B, _ptr(so), _ptr(T), _ptr(C), ctypes.byref(fld), _ptr(v), float(lip), float(r_min), float(tol),
+            int(max_evals), _ptr(near), _ptr(evals), _ptr(flags)))
         return near, evals, flags
 
     def corridor_inflate(self, seg_offsets, waypoints, origin, h: float, values, r_free: float, max_grow: int):
@@ -435,8 +388,7 @@ class Solver:
         bounding box.  Returns (box [S,6] = lo[3] hi[3], faces [6S,4] and face_offsets [S+1] as
         corridor() and corridor_loop() take them, seg_flags [S] and flags [B] of INF_* bits and
         FEAS_NONFINITE)."""
-        so = np.ascontiguousarray(seg_offsets, dtype=np.int32)
-        W = np.ascontiguousarray(waypoints, dtype=np.float64).reshape(-1, 3)
+        so, W, _, _, _ = _csr(seg_offsets, waypoints)
         v = np.ascontiguousarray(values, dtype=np.float32)
         assert v.ndim == 3, "values must be [nz, ny, nx]"
         fld = _lib.Field(origin, h, v.shape[::-1])
@@ -446,11 +398,9 @@ class Solver:
         faces = np.full((6 * S, 4), np.nan, dtype=np.float64)
         fo = np.full(S + 1, -2, dtype=np.int64)
         seg_flags, flags = np.full(S, -2, dtype=np.int32), np.full(B, -2, dtype=np.int32)
-        st = self._L.tgms_corridor_inflate_batch(self._h, B, _ptr(so), _ptr(W), ctypes.byref(fld), _ptr(v),
-                                                 float(r_free), int(max_grow), _ptr(box), _ptr(faces), _ptr(fo),
-                                                 _ptr(seg_flags), _ptr(flags))
-        if st != _lib.OK:
-            raise TgmsError(st, self.last_error())
+        self._check(self._L.tgms_corridor_inflate_batch(
+            self._h, B, _ptr(so), _ptr(W), ctypes.byref(fld), _ptr(v), float(r_free), int(max_grow), _ptr(box),
+            _ptr(faces), _ptr(fo), _ptr(seg_flags), _ptr(flags)))
         return box, faces, fo, seg_flags, flags
 
     def corridor_subdivide(self, seg_offsets, waypoints, origin, h: float, values, r_free: float,
@@ -461,9 +411,7 @@ class Solver:
         pass MAX_SEGMENTS.  Returns the new batch trimmed to its S' segments: (seg_offsets' [B+1],
         waypoints' [S'+B,3], seg_times' [S'] (None without seg_times), parent [S'], seg_flags [S']
         and flags [B] of SUB_* bits and FEAS_NONFINITE)."""
-        so = np.ascontiguousarray(seg_offsets, dtype=np.int32)
-        W = np.ascontiguousarray(waypoints, dtype=np.float64).reshape(-1, 3)
-        T = None if seg_times is None else np.ascontiguousarray(seg_times, dtype=np.float64).reshape(-1)
+        so, W, T, _, _ = _csr(seg_offsets, waypoints, seg_times)
         v = np.ascontiguousarray(values, dtype=np.float32)
         assert v.ndim == 3, "values must be [nz, ny, nx]"
         fld = _lib.Field(origin, h, v.shape[::-1])
@@ -476,11 +424,9 @@ class Solver:
         parent, seg_flags = np.zeros(cap, dtype=np.int32), np.zeros(cap, dtype=np.int32)
         totals = np.zeros(1, dtype=np.int64)
         flags = np.zeros(B, dtype=np.int32)
-        st = self._L.tgms_corridor_subdivide_batch(self._h, B, _ptr(so), _ptr(W), _ptr(T), ctypes.byref(fld), _ptr(v),
-                                                   float(r_free), int(max_depth), _ptr(so2), _ptr(W2), _ptr(T2),
-                                                   _ptr(parent), _ptr(seg_flags), _ptr(totals), _ptr(flags))
-        if st != _lib.OK:
-            raise TgmsError(st, self.last_error())
+        self._check(self._L.tgms_corridor_subdivide_batch(
+            self._h, B, _ptr(so), _ptr(W), _ptr(T), ctypes.byref(fld), _ptr(v), float(r_free), int(max_depth),
+            _ptr(so2), _ptr(W2), _ptr(T2), _ptr(parent), _ptr(seg_flags), _ptr(totals), _ptr(flags)))
         S2 = int(totals[0])
         return so2, W2[:S2 + B], None if T2 is None else T2[:S2], parent[:S2], seg_flags[:S2], flags
 
@@ -495,10 +441,9 @@ class Solver:
         fld = _lib.Field(origin, h, o.shape[::-1])
         values = np.full(o.shape, np.nan, dtype=np.float32)
         d2 = np.zeros(o.shape, dtype=np.int32)
-        st = self._L.tgms_field_edt(self._h, ctypes.byref(fld), _ptr(o), float(max_dist),
-                                    _lib.EDT_SIGNED if signed else 0, _ptr(values), _ptr(d2))
-        if st != _lib.OK:
-            raise TgmsError(st, self.last_error())
+        self._check(self._L.tgms_field_edt(
+            self._h, ctypes.byref(fld), _ptr(o), float(max_dist), _lib.EDT_SIGNED if signed else 0, _ptr(values),
+            _ptr(d2)))
         return values, d2
 
     def field_edt_work_size(self, origin, h: float, n, signed: bool = False) -> int:
@@ -522,10 +467,8 @@ class Solver:
                iters: int = 10, coeffs: bool = True):
         """Time-allocation refinement on the GPU (include/tgms.h tgms_refine_batch).
         Returns (T [S], coeffs [S,3,8] or None, cost [B], status [B], worst)."""
-        so = np.ascontiguousarray(seg_offsets, dtype=np.int32)
-        W = np.ascontiguousarray(waypoints, dtype=np.float64).reshape(-1, 3)
+        so, W, _, _, ED = _csr(seg_offsets, waypoints, end_derivs=end_derivs)
         T = np.array(seg_times, dtype=np.float64).reshape(-1)
-        ED = None if end_derivs is None else np.ascontiguousarray(end_derivs, dtype=np.float64).reshape(-1, 18)
         B = so.shape[0] - 1
         C = np.zeros((int(so[-1]), 3, 8), dtype=np.float64) if coeffs else None
         cost = np.zeros(max(B, 1), dtype=np.float64)
@@ -539,124 +482,99 @@ class Solver:
     # -------------------------------------------------------------- device API
     def refine_uniform_device(self, B: int, M: int, d_waypoints, d_seg_times, d_seg_times_out, k_T: float,
                               eta: float, d_cost=None, d_status=None, d_end_derivs=None, stream: int = 0) -> None:
-        st = self._L.tgms_refine_uniform_device(self._h, int(B), int(M), _ptr(d_waypoints), _ptr(d_seg_times),
-                                                _ptr(d_end_derivs), float(k_T), float(eta), _ptr(d_seg_times_out),
-                                                _ptr(d_cost), _ptr(d_status), ctypes.c_void_p(stream))
-        if st != _lib.OK:
-            raise TgmsError(st, self.last_error())
+        self._check(self._L.tgms_refine_uniform_device(
+            self._h, int(B), int(M), _ptr(d_waypoints), _ptr(d_seg_times), _ptr(d_end_derivs), float(k_T), float(eta),
+            _ptr(d_seg_times_out), _ptr(d_cost), _ptr(d_status), ctypes.c_void_p(stream)))
 
     def refine_loop_device(self, h_seg_offsets, d_seg_offsets, d_waypoints, d_seg_times, k_T: float, eta: float,
                            iters: int, d_coeffs=None, d_cost=None, d_status=None, d_end_derivs=None,
                            stream: int = 0) -> None:
         so = np.ascontiguousarray(h_seg_offsets, dtype=np.int32)
-        st = self._L.tgms_refine_loop_device(self._h, int(so.shape[0] - 1), _ptr(so), _ptr(d_seg_offsets),
-                                             _ptr(d_waypoints), _ptr(d_seg_times), _ptr(d_end_derivs), float(k_T),
-                                             float(eta), int(iters), _ptr(d_coeffs), _ptr(d_cost), _ptr(d_status),
-                                             ctypes.c_void_p(stream))
-        if st != _lib.OK:
-            raise TgmsError(st, self.last_error())
+        self._check(self._L.tgms_refine_loop_device(
+            self._h, int(so.shape[0] - 1), _ptr(so), _ptr(d_seg_offsets), _ptr(d_waypoints), _ptr(d_seg_times),
+            _ptr(d_end_derivs), float(k_T), float(eta), int(iters), _ptr(d_coeffs), _ptr(d_cost), _ptr(d_status),
+            ctypes.c_void_p(stream)))
 
     def refine_batch_device(self, h_seg_offsets, d_seg_offsets, d_waypoints, d_seg_times, d_seg_times_out,
                             k_T: float, eta: float, d_cost=None, d_status=None, d_end_derivs=None,
                             stream: int = 0) -> None:
         so = np.ascontiguousarray(h_seg_offsets, dtype=np.int32)
-        st = self._L.tgms_refine_batch_device(self._h, int(so.shape[0] - 1), _ptr(so), _ptr(d_seg_offsets),
-                                              _ptr(d_waypoints), _ptr(d_seg_times), _ptr(d_end_derivs), float(k_T),
-                                              float(eta), _ptr(d_seg_times_out), _ptr(d_cost), _ptr(d_status),
-                                              ctypes.c_void_p(stream))
-        if st != _lib.OK:
-            raise TgmsError(st, self.last_error())
+        self._check(self._L.tgms_refine_batch_device(
+            self._h, int(so.shape[0] - 1), _ptr(so), _ptr(d_seg_offsets), _ptr(d_waypoints), _ptr(d_seg_times),
+            _ptr(d_end_derivs), float(k_T), float(eta), _ptr(d_seg_times_out), _ptr(d_cost), _ptr(d_status),
+            ctypes.c_void_p(stream)))
 
     def solve_uniform_device(self, B: int, M: int, d_waypoints, d_seg_times, d_coeffs, d_status=None,
                              d_end_derivs=None, stream: int = 0) -> None:
-        st = self._L.tgms_solve_uniform_device(self._h, int(B), int(M), _ptr(d_waypoints), _ptr(d_seg_times),
-                                               _ptr(d_end_derivs), _ptr(d_coeffs), _ptr(d_status),
-                                               ctypes.c_void_p(stream))
-        if st != _lib.OK:
-            raise TgmsError(st, self.last_error())
+        self._check(self._L.tgms_solve_uniform_device(
+            self._h, int(B), int(M), _ptr(d_waypoints), _ptr(d_seg_times), _ptr(d_end_derivs), _ptr(d_coeffs),
+            _ptr(d_status), ctypes.c_void_p(stream)))
 
     def solve_batch_device(self, h_seg_offsets, d_seg_offsets, d_waypoints, d_seg_times, d_coeffs,
                            d_status=None, d_end_derivs=None, stream: int = 0) -> None:
         so = np.ascontiguousarray(h_seg_offsets, dtype=np.int32)
-        st = self._L.tgms_solve_batch_device(self._h, int(so.shape[0] - 1), _ptr(so), _ptr(d_seg_offsets),
-                                             _ptr(d_waypoints), _ptr(d_seg_times), _ptr(d_end_derivs),
-                                             _ptr(d_coeffs), _ptr(d_status), ctypes.c_void_p(stream))
-        if st != _lib.OK:
-            raise TgmsError(st, self.last_error())
+        self._check(self._L.tgms_solve_batch_device(
+            self._h, int(so.shape[0] - 1), _ptr(so), _ptr(d_seg_offsets), _ptr(d_waypoints), _ptr(d_seg_times),
+            _ptr(d_end_derivs), _ptr(d_coeffs), _ptr(d_status), ctypes.c_void_p(stream)))
 
     def solve_batch_multi_device(self, h_seg_offsets, d_seg_offsets, d_waypoints, d_seg_times, d_coeffs,
                                  d_status=None, d_end_derivs=None, stream: int = 0) -> None:
         so = np.ascontiguousarray(h_seg_offsets, dtype=np.int32)
-        st = self._L.tgms_solve_batch_multi_device(self._h, int(so.shape[0] - 1), _ptr(so), _ptr(d_seg_offsets),
-                                                   _ptr(d_waypoints), _ptr(d_seg_times), _ptr(d_end_derivs),
-                                                   _ptr(d_coeffs), _ptr(d_status), ctypes.c_void_p(stream))
-        if st != _lib.OK:
-            raise TgmsError(st, self.last_error())
+        self._check(self._L.tgms_solve_batch_multi_device(
+            self._h, int(so.shape[0] - 1), _ptr(so), _ptr(d_seg_offsets), _ptr(d_waypoints), _ptr(d_seg_times),
+            _ptr(d_end_derivs), _ptr(d_coeffs), _ptr(d_status), ctypes.c_void_p(stream)))
 
     def refine_loop_multi_device(self, h_seg_offsets, d_seg_offsets, d_waypoints, d_seg_times, k_T: float,
                                  eta: float, iters: int, d_coeffs=None, d_cost=None, d_status=None,
                                  d_end_derivs=None, stream: int = 0) -> None:
         so = np.ascontiguousarray(h_seg_offsets, dtype=np.int32)
-        st = self._L.tgms_refine_loop_multi_device(self._h, int(so.shape[0] - 1), _ptr(so), _ptr(d_seg_offsets),
-                                                   _ptr(d_waypoints), _ptr(d_seg_times), _ptr(d_end_derivs),
-                                                   float(k_T), float(eta), int(iters), _ptr(d_coeffs),
-                                                   _ptr(d_cost), _ptr(d_status), ctypes.c_void_p(stream))
-        if st != _lib.OK:
-            raise TgmsError(st, self.last_error())
+        self._check(self._L.tgms_refine_loop_multi_device(
+            self._h, int(so.shape[0] - 1), _ptr(so), _ptr(d_seg_offsets), _ptr(d_waypoints), _ptr(d_seg_times),
+            _ptr(d_end_derivs), float(k_T), float(eta), int(iters), _ptr(d_coeffs), _ptr(d_cost), _ptr(d_status),
+            ctypes.c_void_p(stream)))
 
     def sample_device(self, B: int, d_seg_offsets, d_waypoints, d_seg_times, d_coeffs, dt: float,
                       d_sample_offsets, d_out, d_end_derivs=None, yaw_mode: int = _lib.YAW_CONSTANT,
                       yaw_const: float = 0.0, stream: int = 0) -> None:
-        st = self._L.tgms_sample_batch_device(self._h, int(B), _ptr(d_seg_offsets), _ptr(d_waypoints),
-                                              _ptr(d_seg_times), _ptr(d_end_derivs), _ptr(d_coeffs), float(dt),
-                                              int(yaw_mode), float(yaw_const), _ptr(d_sample_offsets),
-                                              _ptr(d_out), ctypes.c_void_p(stream))
-        if st != _lib.OK:
-            raise TgmsError(st, self.last_error())
+        self._check(self._L.tgms_sample_batch_device(
+            self._h, int(B), _ptr(d_seg_offsets), _ptr(d_waypoints), _ptr(d_seg_times), _ptr(d_end_derivs),
+            _ptr(d_coeffs), float(dt), int(yaw_mode), float(yaw_const), _ptr(d_sample_offsets), _ptr(d_out),
+            ctypes.c_void_p(stream)))
 
     def extrema_device(self, B: int, d_seg_offsets, d_waypoints, d_seg_times, d_coeffs, dt: float,
                        limits: Optional[_lib.Limits] = None, d_extrema=None, d_flags=None, d_end_derivs=None,
                        stream: int = 0) -> None:
         """tgms_extrema_batch_device: d_extrema [B,10] fp64 and / or d_flags [B] int32 (at
         least one); `limits` is read now, so it may change before the kernel runs."""
-        st = self._L.tgms_extrema_batch_device(self._h, int(B), _ptr(d_seg_offsets), _ptr(d_waypoints),
-                                               _ptr(d_seg_times), _ptr(d_end_derivs), _ptr(d_coeffs), float(dt),
-                                               None if limits is None else ctypes.byref(limits),
-                                               _ptr(d_extrema), _ptr(d_flags), ctypes.c_void_p(stream))
-        if st != _lib.OK:
-            raise TgmsError(st, self.last_error())
+        self._check(self._L.tgms_extrema_batch_device(
+            self._h, int(B), _ptr(d_seg_offsets), _ptr(d_waypoints), _ptr(d_seg_times), _ptr(d_end_derivs),
+            _ptr(d_coeffs), float(dt), None if limits is None else ctypes.byref(limits), _ptr(d_extrema), _ptr(d_flags),
+            ctypes.c_void_p(stream)))
 
     def bounds_device(self, B: int, d_seg_offsets, d_seg_times, d_coeffs, limits: Optional[_lib.Limits] = None,
                       d_extrema=None, d_flags=None, stream: int = 0) -> None:
         """tgms_bounds_batch_device: d_extrema [B,10] fp64 and / or d_flags [B] int32 (at
         least one); `limits` is read now, so it may change before the kernel runs."""
-        st = self._L.tgms_bounds_batch_device(self._h, int(B), _ptr(d_seg_offsets), _ptr(d_seg_times),
-                                              _ptr(d_coeffs), None if limits is None else ctypes.byref(limits),
-                                              _ptr(d_extrema), _ptr(d_flags), ctypes.c_void_p(stream))
-        if st != _lib.OK:
-            raise TgmsError(st, self.last_error())
+        self._check(self._L.tgms_bounds_batch_device(
+            self._h, int(B), _ptr(d_seg_offsets), _ptr(d_seg_times), _ptr(d_coeffs),
+            None if limits is None else ctypes.byref(limits), _ptr(d_extrema), _ptr(d_flags), ctypes.c_void_p(stream)))
 
     def thrust_device(self, B: int, d_seg_offsets, d_seg_times, d_coeffs, g: float = 9.80665,
                       limits: Optional[_lib.ThrustLimits] = None, d_rec=None, d_flags=None, stream: int = 0) -> None:
         """tgms_thrust_batch_device: d_rec [B,6] fp64 and / or d_flags [B] int32 (at least
         one); g and `limits` are read now, so they may change before the kernel runs."""
-        st = self._L.tgms_thrust_batch_device(self._h, int(B), _ptr(d_seg_offsets), _ptr(d_seg_times),
-                                              _ptr(d_coeffs), float(g),
-                                              None if limits is None else ctypes.byref(limits),
-                                              _ptr(d_rec), _ptr(d_flags), ctypes.c_void_p(stream))
-        if st != _lib.OK:
-            raise TgmsError(st, self.last_error())
+        self._check(self._L.tgms_thrust_batch_device(
+            self._h, int(B), _ptr(d_seg_offsets), _ptr(d_seg_times), _ptr(d_coeffs), float(g),
+            None if limits is None else ctypes.byref(limits), _ptr(d_rec), _ptr(d_flags), ctypes.c_void_p(stream)))
 
     def rate_device(self, B: int, d_seg_offsets, d_seg_times, d_coeffs, g: float = 9.80665,
                     omega_limit: float = float("inf"), d_rec=None, d_seg_rec=None, d_flags=None,
                     stream: int = 0) -> None:
         """tgms_rate_batch_device: d_rec [B,2] fp64, d_seg_rec [S,2] fp64 and / or d_flags [B]
         int32 (at least one); g and `omega_limit` travel as kernel arguments."""
-        st = self._L.tgms_rate_batch_device(self._h, int(B), _ptr(d_seg_offsets), _ptr(d_seg_times),
-                                            _ptr(d_coeffs), float(g), float(omega_limit), _ptr(d_rec),
-                                            _ptr(d_seg_rec), _ptr(d_flags), ctypes.c_void_p(stream))
-        if st != _lib.OK:
-            raise TgmsError(st, self.last_error())
+        self._check(self._L.tgms_rate_batch_device(
+            self._h, int(B), _ptr(d_seg_offsets), _ptr(d_seg_times), _ptr(d_coeffs), float(g), float(omega_limit),
+            _ptr(d_rec), _ptr(d_seg_rec), _ptr(d_flags), ctypes.c_void_p(stream)))
 
     def dilate_device(self, B: int, d_seg_offsets, d_seg_times, d_coeffs, g: float = 9.80665,
                       limits: Optional[_lib.Limits] = None, tlimits: Optional[_lib.ThrustLimits] = None,
@@ -665,14 +583,11 @@ class Solver:
         """tgms_dilate_batch_device: d_scale [B] fp64, d_active [B] int32, d_flags [B] int32,
         d_seg_times_out [S] fp64, d_coeffs_out [S,3,8] fp64 (at least one; the last two may be the
         inputs themselves); g and the limits are read now, so they may change before the kernel runs."""
-        st = self._L.tgms_dilate_batch_device(self._h, int(B), _ptr(d_seg_offsets), _ptr(d_seg_times),
-                                              _ptr(d_coeffs), float(g),
-                                              None if limits is None else ctypes.byref(limits),
-                                              None if tlimits is None else ctypes.byref(tlimits), float(s_lo),
-                                              float(s_hi), _ptr(d_scale), _ptr(d_active), _ptr(d_flags),
-                                              _ptr(d_seg_times_out), _ptr(d_coeffs_out), ctypes.c_void_p(stream))
-        if st != _lib.OK:
-            raise TgmsError(st, self.last_error())
+        self._check(self._L.tgms_dilate_batch_device(
+            self._h, int(B), _ptr(d_seg_offsets), _ptr(d_seg_times), _ptr(d_coeffs), float(g),
+            None if limits is None else ctypes.byref(limits), None if tlimits is None else ctypes.byref(tlimits),
+            float(s_lo), float(s_hi), _ptr(d_scale), _ptr(d_active), _ptr(d_flags), _ptr(d_seg_times_out),
+            _ptr(d_coeffs_out), ctypes.c_void_p(stream)))
 
     def corridor_device(self, B: int, d_seg_offsets, d_seg_times, d_coeffs, F: int, d_faces, d_face_offsets=None,
                         r: float = 0.0, d_rec=None, d_where=None, d_seg_rec=None, d_seg_face=None, d_flags=None,
@@ -680,12 +595,10 @@ class Solver:
         """tgms_corridor_batch_device: d_faces [F,4] fp64, d_face_offsets [S+1] int64 or None (all
         F faces apply to every segment); d_rec [B,2] fp64, d_where [B,2] int32, d_seg_rec [S,2]
         fp64, d_seg_face [S] int32, d_flags [B] int32 (at least one)."""
-        st = self._L.tgms_corridor_batch_device(self._h, int(B), _ptr(d_seg_offsets), _ptr(d_seg_times),
-                                                _ptr(d_coeffs), int(F), _ptr(d_faces), _ptr(d_face_offsets),
-                                                float(r), _ptr(d_rec), _ptr(d_where), _ptr(d_seg_rec),
-                                                _ptr(d_seg_face), _ptr(d_flags), ctypes.c_void_p(stream))
-        if st != _lib.OK:
-            raise TgmsError(st, self.last_error())
+        self._check(self._L.tgms_corridor_batch_device(
+            self._h, int(B), _ptr(d_seg_offsets), _ptr(d_seg_times), _ptr(d_coeffs), int(F), _ptr(d_faces),
+            _ptr(d_face_offsets), float(r), _ptr(d_rec), _ptr(d_where), _ptr(d_seg_rec), _ptr(d_seg_face),
+            _ptr(d_flags), ctypes.c_void_p(stream)))
 
     def corridor_split_device(self, B: int, d_seg_offsets, d_waypoints, d_seg_times, d_coeffs, F: int, d_faces,
                               d_face_offsets, d_seg_rec, d_seg_face, r: float, mode: int, min_frac: float,
@@ -697,13 +610,11 @@ class Solver:
         [2F,4], d_face_offsets_out [2S+1] int64, d_parent [2S] int32, d_totals [2] int64 = S' F',
         d_flags [B] int32); shared mode (d_face_offsets None) takes no face outputs.  Not
         capturable: it grows handle scratch with B."""
-        st = self._L.tgms_corridor_split_batch_device(
+        self._check(self._L.tgms_corridor_split_batch_device(
             self._h, int(B), _ptr(d_seg_offsets), _ptr(d_waypoints), _ptr(d_seg_times), _ptr(d_coeffs), int(F),
             _ptr(d_faces), _ptr(d_face_offsets), _ptr(d_seg_rec), _ptr(d_seg_face), float(r), int(mode),
             float(min_frac), _ptr(d_seg_offsets_out), _ptr(d_waypoints_out), _ptr(d_seg_times_out), _ptr(d_faces_out),
-            _ptr(d_face_offsets_out), _ptr(d_parent), _ptr(d_totals), _ptr(d_flags), ctypes.c_void_p(stream))
-        if st != _lib.OK:
-            raise TgmsError(st, self.last_error())
+            _ptr(d_face_offsets_out), _ptr(d_parent), _ptr(d_totals), _ptr(d_flags), ctypes.c_void_p(stream)))
 
     def cut_device(self, B: int, d_seg_offsets, d_waypoints, d_seg_times, d_coeffs, d_t_cut, min_frac: float,
                    d_seg_offsets_out, d_waypoints_out, d_seg_times_out, d_end_derivs_out, d_totals,
@@ -713,13 +624,11 @@ class Solver:
         d_waypoints_out [S+B,3], d_seg_times_out [S], d_end_derivs_out [B,18], d_coeffs_out [S,3,8],
         d_parent [S] int32, d_t0_out [B], d_totals [1] int64 = S', d_flags [B] int32).  Not
         capturable: it grows handle scratch with B."""
-        st = self._L.tgms_cut_batch_device(
+        self._check(self._L.tgms_cut_batch_device(
             self._h, int(B), _ptr(d_seg_offsets), _ptr(d_waypoints), _ptr(d_seg_times), _ptr(d_end_derivs),
             _ptr(d_coeffs), _ptr(d_t_cut), float(min_frac), _ptr(d_seg_offsets_out), _ptr(d_waypoints_out),
             _ptr(d_seg_times_out), _ptr(d_end_derivs_out), _ptr(d_coeffs_out), _ptr(d_parent), _ptr(d_t0_out),
-            _ptr(d_totals), _ptr(d_flags), ctypes.c_void_p(stream))
-        if st != _lib.OK:
-            raise TgmsError(st, self.last_error())
+            _ptr(d_totals), _ptr(d_flags), ctypes.c_void_p(stream)))
 
     def separation_device(self, B: int, d_seg_offsets, d_seg_times, d_coeffs, P: int, d_pairs=None,
                           d_start_times=None, scale=None, r_min: float = 0.0, d_sep=None, d_flags=None,
@@ -728,12 +637,9 @@ class Solver:
         one); d_pairs int32 [P,2] or None for all pairs (P = B (B - 1) / 2); `scale` (host,
         three values or None) and r_min are read now."""
         sc = None if scale is None else np.ascontiguousarray(scale, dtype=np.float64).reshape(3)
-        st = self._L.tgms_separation_batch_device(self._h, int(B), _ptr(d_seg_offsets), _ptr(d_seg_times),
-                                                  _ptr(d_coeffs), _ptr(d_start_times), int(P), _ptr(d_pairs),
-                                                  _ptr(sc), float(r_min), _ptr(d_sep), _ptr(d_flags),
-                                                  ctypes.c_void_p(stream))
-        if st != _lib.OK:
-            raise TgmsError(st, self.last_error())
+        self._check(self._L.tgms_separation_batch_device(
+            self._h, int(B), _ptr(d_seg_offsets), _ptr(d_seg_times), _ptr(d_coeffs), _ptr(d_start_times), int(P),
+            _ptr(d_pairs), _ptr(sc), float(r_min), _ptr(d_sep), _ptr(d_flags), ctypes.c_void_p(stream)))
 
     def neighbors_device(self, B: int, d_seg_offsets, d_seg_times, d_coeffs, r_min: float, d_start_times=None,
                          scale=None, d_near=None, d_nbr=None, d_count=None, d_tested=None, d_flags=None,
@@ -742,12 +648,10 @@ class Solver:
         [B] int32 (at least one of near, nbr, count, flags); `scale` (host, three values or
         None) and r_min are read now.  Not capturable: it grows handle scratch with B."""
         sc = None if scale is None else np.ascontiguousarray(scale, dtype=np.float64).reshape(3)
-        st = self._L.tgms_neighbors_batch_device(self._h, int(B), _ptr(d_seg_offsets), _ptr(d_seg_times),
-                                                 _ptr(d_coeffs), _ptr(d_start_times), _ptr(sc), float(r_min),
-                                                 _ptr(d_near), _ptr(d_nbr), _ptr(d_count), _ptr(d_tested),
-                                                 _ptr(d_flags), ctypes.c_void_p(stream))
-        if st != _lib.OK:
-            raise TgmsError(st, self.last_error())
+        self._check(self._L.tgms_neighbors_batch_device(
+            self._h, int(B), _ptr(d_seg_offsets), _ptr(d_seg_times), _ptr(d_coeffs), _ptr(d_start_times), _ptr(sc),
+            float(r_min), _ptr(d_near), _ptr(d_nbr), _ptr(d_count), _ptr(d_tested), _ptr(d_flags),
+            ctypes.c_void_p(stream)))
 
     def clearance_device(self, B: int, d_seg_offsets, d_seg_times, d_coeffs, K: int, d_obstacles, r_min: float,
                          scale=None, d_near=None, d_obs=None, d_count=None, d_tested=None, d_flags=None,
@@ -756,13 +660,10 @@ class Solver:
         d_tested / d_flags [B] int32 (at least one of near, obs, count, flags); `scale` (host, three
         values or None) and r_min are read now.  Not capturable: it grows handle scratch with B, K."""
         sc = None if scale is None else np.ascontiguousarray(scale, dtype=np.float64).reshape(3)
-        st = self._L.tgms_clearance_batch_device(self._h, int(B), _ptr(d_seg_offsets), _ptr(d_seg_times),
-                                                 _ptr(d_coeffs), int(K), _ptr(d_obstacles), _ptr(sc), float(r_min),
-                                                 _ptr(d_near), _ptr(d_obs), _ptr(d_count), _ptr(d_tested),
-                                                 _ptr(d_flags), ctypes.c_void_p(stream))
-        if st != _lib.OK:
-            raise TgmsError(st, self.last_error())
-
+        self._check(self._L.tgms_clearance_batch_device(
+            self._h, int(B), _ptr(d_seg_offsets), _ptr(d_seg_times), _ptr(d_coeffs), int(K), _ptr(d_obstacles),
+            _ptr(sc), float(r_min), _ptr(d_near), _ptr(d_obs), _ptr(d_count), _ptr(d_tested), _ptr(d_flags),
+            ctypes.c_void_p(stream)))
 
     def field_clearance_device(self, B: int, d_seg_offsets, d_seg_times, d_coeffs, origin, h: float, n, d_values,
                                lip: float, r_min: float, tol: float, max_evals: int, d_near=None, d_evals=None,
@@ -771,22 +672,18 @@ class Solver:
         [B,2] fp64, d_evals / d_flags [B] int32 (at least one of the three); the grid, lip, r_min,
         tol and max_evals are read now.  Capturable with lip > 0; lip == 0 uses handle scratch."""
         fld = _lib.Field(origin, h, n)
-        st = self._L.tgms_field_clearance_batch_device(self._h, int(B), _ptr(d_seg_offsets), _ptr(d_seg_times),
-                                                       _ptr(d_coeffs), ctypes.byref(fld), _ptr(d_values), float(lip),
-                                                       float(r_min), float(tol), int(max_evals), _ptr(d_near),
-                                                       _ptr(d_evals), _ptr(d_flags), ctypes.c_void_p(stream))
-        if st != _lib.OK:
-            raise TgmsError(st, self.last_error())
+        self._check(self._L.tgms_field_clearance_batch_device(
+            self._h, int(B), _ptr(d_seg_offsets), _ptr(d_seg_times), _ptr(d_coeffs), ctypes.byref(fld), _ptr(d_values),
+            float(lip), float(r_min), float(tol), int(max_evals), _ptr(d_near), _ptr(d_evals), _ptr(d_flags),
+            ctypes.c_void_p(stream)))
 
     def field_occupancy_device(self, origin, h: float, n, d_values, r_free: float, d_table, stream: int = 0) -> None:
         """tgms_field_occupancy_device: n = (nx, ny, nz), d_values fp32 with x fastest; d_table int32
         [(nz+1),(ny+1),(nx+1)] receives the summed-volume table of the nodes below float32(r_free).
         Three launches, no handle scratch: capturable."""
         fld = _lib.Field(origin, h, n)
-        st = self._L.tgms_field_occupancy_device(self._h, ctypes.byref(fld), _ptr(d_values), float(r_free),
-                                                 _ptr(d_table), ctypes.c_void_p(stream))
-        if st != _lib.OK:
-            raise TgmsError(st, self.last_error())
+        self._check(self._L.tgms_field_occupancy_device(
+            self._h, ctypes.byref(fld), _ptr(d_values), float(r_free), _ptr(d_table), ctypes.c_void_p(stream)))
 
     def field_edt_device(self, origin, h: float, n, d_occ, max_dist: float, d_work, d_values=None, d_d2=None,
                          signed: bool = False, stream: int = 0) -> None:
@@ -794,11 +691,9 @@ class Solver:
         int32 of the same shape (at least one); d_work of field_edt_work_size bytes.  Three launches
         (six signed), no handle scratch: capturable."""
         fld = _lib.Field(origin, h, n)
-        st = self._L.tgms_field_edt_device(self._h, ctypes.byref(fld), _ptr(d_occ), float(max_dist),
-                                           _lib.EDT_SIGNED if signed else 0, _ptr(d_values), _ptr(d_d2), _ptr(d_work),
-                                           ctypes.c_void_p(stream))
-        if st != _lib.OK:
-            raise TgmsError(st, self.last_error())
+        self._check(self._L.tgms_field_edt_device(
+            self._h, ctypes.byref(fld), _ptr(d_occ), float(max_dist), _lib.EDT_SIGNED if signed else 0, _ptr(d_values),
+            _ptr(d_d2), _ptr(d_work), ctypes.c_void_p(stream)))
 
     def corridor_inflate_device(self, B: int, d_seg_offsets, d_waypoints, origin, h: float, n, d_table, max_grow: int,
                                 d_box=None, d_faces=None, d_face_offsets=None, d_seg_flags=None, d_flags=None,
@@ -807,12 +702,10 @@ class Solver:
         d_box [S,6] int32, d_faces [6S,4] fp64, d_face_offsets [S+1] int64, d_seg_flags [S] and d_flags
         [B] int32 (at least one).  One launch, no handle scratch: capturable."""
         fld = _lib.Field(origin, h, n)
-        st = self._L.tgms_corridor_inflate_batch_device(self._h, int(B), _ptr(d_seg_offsets), _ptr(d_waypoints),
-                                                        ctypes.byref(fld), _ptr(d_table), int(max_grow), _ptr(d_box),
-                                                        _ptr(d_faces), _ptr(d_face_offsets), _ptr(d_seg_flags),
-                                                        _ptr(d_flags), ctypes.c_void_p(stream))
-        if st != _lib.OK:
-            raise TgmsError(st, self.last_error())
+        self._check(self._L.tgms_corridor_inflate_batch_device(
+            self._h, int(B), _ptr(d_seg_offsets), _ptr(d_waypoints), ctypes.byref(fld), _ptr(d_table), int(max_grow),
+            _ptr(d_box), _ptr(d_faces), _ptr(d_face_offsets), _ptr(d_seg_flags), _ptr(d_flags),
+            ctypes.c_void_p(stream)))
 
     def corridor_subdivide_device(self, B: int, d_seg_offsets, d_waypoints, origin, h: float, n, d_table,
                                   max_depth: int, d_seg_offsets_out, d_waypoints_out, d_totals, d_seg_times=None,
@@ -824,12 +717,10 @@ class Solver:
         d_seg_flags_out [cap] int32, d_totals [1] int64 = S', d_flags [B] int32.  Not capturable: it
         grows handle scratch with B."""
         fld = _lib.Field(origin, h, n)
-        st = self._L.tgms_corridor_subdivide_batch_device(
+        self._check(self._L.tgms_corridor_subdivide_batch_device(
             self._h, int(B), _ptr(d_seg_offsets), _ptr(d_waypoints), _ptr(d_seg_times), ctypes.byref(fld),
             _ptr(d_table), int(max_depth), _ptr(d_seg_offsets_out), _ptr(d_waypoints_out), _ptr(d_seg_times_out),
-            _ptr(d_parent), _ptr(d_seg_flags_out), _ptr(d_totals), _ptr(d_flags), ctypes.c_void_p(stream))
-        if st != _lib.OK:
-            raise TgmsError(st, self.last_error())
+            _ptr(d_parent), _ptr(d_seg_flags_out), _ptr(d_totals), _ptr(d_flags), ctypes.c_void_p(stream)))
 
 
 def sample_count(total_T: float, dt: float) -> int:
