@@ -1200,6 +1200,115 @@ tgms_status tgms_corridor_subdivide_batch(tgms_handle* h, int32_t B, const int32
                                           double* seg_times_out, int32_t* parent, int32_t* seg_flags_out,
                                           int64_t* totals, int32_t* flags);
 
+/* ---- corridor re-route: detour blocked legs through the free nodes of the map ----
+ * What the subdivision asks of the planner when a leaf stays TGMS_SUB_BLOCKED: the chord itself
+ * passes an obstacle, so the leg needs other waypoints.  For every leg the inflation would report
+ * TGMS_INF_BLOCKED for, the call searches a shortest 6-neighbour path through the free nodes of a
+ * bounded window of the map, reduces it to at most max_pieces pieces whose seeds are free, and
+ * rebuilds the batch -- seg_offsets, waypoints, seg_times, parents -- on the device, ready for
+ * tgms_corridor_inflate_batch_device and the solve.  The result is integers and doubles with
+ * stated rounding: the host backend and the device agree to the bit, and no result depends on the
+ * algorithm of the search or on the launch shape.
+ *   Inputs.  B, d_seg_offsets, d_waypoints [S+B][3], d_seg_times [S] (NULL together with
+ * d_seg_times_out), the grid `field` and the table of tgms_field_occupancy_device as in the
+ * subdivision call; margin >= 0; max_pieces in 2..8.  The host-pointer call takes values and
+ * r_free and builds the table itself.  There is no flag input: the call decides from the same
+ * doubles the inflation will see.
+ *   Candidate.  A leg (w0, w1) is searched when every coordinate is finite, w0 and w1 differ in at
+ * least one axis bit for bit, its seed (the inflation's rule) lies in the grid and holds a non-free
+ * node.  Every other leg is copied bit for bit, with TGMS_FEAS_NONFINITE, TGMS_RRT_OUTSIDE, or
+ * TGMS_RRT_BLOCKED (w0 == w1 in a blocked seed) where the inflation will say so, else 0.
+ *   Window.  The seed [lo_a .. hi_a] widened by margin nodes on each side and clipped to the grid.
+ * More than TGMS_RRT_WINDOW_NODES nodes: TGMS_RRT_WINDOW.  The cap is part of the ABI because the
+ * flags depend on it.
+ *   End nodes.  A is the nearest node to w0: per axis floor((w0_a - origin_a) / h + 0.5), each
+ * operation a separately rounded IEEE fp64 operation, no fused multiply-add, clamped to the seed;
+ * Z the same for w1.  A or Z not free: TGMS_RRT_ENDS -- the waypoint itself sits beside an
+ * obstacle and the planner must move it.
+ *   Distance.  dist(q) is the least number of 6-neighbour steps from Z to q through free nodes of
+ * the window, an exact integer.  A unreachable: TGMS_RRT_NOPATH; the caller grows margin.
+ *   Path.  N_0 = A; N_(i+1) is the first neighbour of N_i in the order +x -x +y -y +z -z that lies
+ * in the window, is free and has dist = dist(N_i) - 1; the last node is Z.
+ *   Points.  Q_0 = w0; Q_(1+i) = origin_a + h index_a of N_i per axis (product and sum each
+ * rounded); the last point is w1.  Q_1 is dropped if it equals Q_0 bit for bit, then the
+ * last-but-one point if it equals the last.
+ *   Pieces.  First-fail greedy.  From the anchor Q_a (first Q_0) the points Q_(a+1), Q_(a+2), ... are
+ * tested in order: clear(Q_a, Q_j) is the subdivision's predicate, the seed of the two points lies
+ * in the grid and holds no non-free node.  When every remaining point is clear the last piece ends
+ * at w1.  Otherwise the first j that fails ends the piece at Q_(j-1), the next anchor; but j == a +
+ * 1 sets TGMS_RRT_ENDS, and an anchor that would make more than max_pieces pieces sets
+ * TGMS_RRT_LONG.  The greedy stops at the first of these, in this order.  p is the number of
+ * pieces; a re-routed leg has p >= 2 because (Q_0, last) is the leg's own blocked seed.
+ *   Budget.  A trajectory whose legs would sum to more than TGMS_MAX_SEGMENTS -- p for a re-routed
+ * leg, 1 otherwise -- is copied whole with TGMS_RRT_FULL: all or nothing, so the rule does not
+ * depend on the order of the legs (the subdivision's reason).
+ *   Times.  len(u, v) = sqrt((dx dx + dy dy) + dz dz), differences, products and sums each rounded,
+ * the root correctly rounded.  A piece gets T_s (len(piece) / len(w0, w1)), quotient and product
+ * each rounded once; a copied leg keeps its time bit for bit.
+ *   Output, as in the subdivision call: d_seg_offsets_out [B+1], d_waypoints_out [S'+B][3],
+ * d_seg_times_out [S'], d_parent [S'], d_seg_flags_out [S'], d_totals [1] = S', d_flags [B]; and
+ * d_hops [S] per INPUT segment: dist(A) where the search reached A (also under TGMS_RRT_LONG,
+ * TGMS_RRT_ENDS of the greedy and TGMS_RRT_FULL), else TGMS_NEAR_NONE.  d_parent, d_seg_flags_out,
+ * d_hops, d_flags and the pair of times are nullable.  The caller provides min(max_pieces S,
+ * TGMS_MAX_SEGMENTS B) segment rows and B more waypoint rows.
+ *   Flags.  Every piece of a re-routed leg has flag 0.  A candidate that is kept whole carries
+ * TGMS_RRT_BLOCKED and its reason (WINDOW, ENDS, NOPATH or LONG); under TGMS_RRT_FULL it carries
+ * TGMS_RRT_BLOCKED alone.  d_flags[b] is the OR of the trajectory's segment flags, with
+ * TGMS_RRT_DONE (it gained a segment) and TGMS_RRT_FULL.
+ *   Guarantees.  (1) An output segment without a flag has a clear seed, so phi(p) >= (float)r_free
+ * on its chord.  (2) tgms_corridor_inflate_batch on the output reports TGMS_INF_BLOCKED exactly on
+ * the segments that carry TGMS_RRT_BLOCKED and TGMS_INF_OUTSIDE exactly on those that carry
+ * TGMS_RRT_OUTSIDE.  (3) Every piece of a re-routed leg has flag 0.  (4) No result depends on the
+ * launch shape, and a repeated call gives the same bits.
+ *   In the device call a segment count outside 1..TGMS_MAX_SEGMENTS becomes the subdivision's
+ * placeholder row; only such offsets can make the output exceed the capacities, and rows beyond
+ * them are not written.
+ *   TGMS_ERR_INVALID_ARG: the grid rules of the inflation call; r_free not finite; margin < 0;
+ * max_pieces outside 2..8; a NULL input or required output; exactly one of the two time arrays
+ * NULL; an fp64 or int64 array that is not 16-byte aligned.  B == 0 is TGMS_OK, writes
+ * d_seg_offsets_out[0] = 0 and d_totals = 0 and nothing else.
+ *   The device entry point is tgms_corridor_reroute_batch_dev -- deliberately not `_device`: the
+ * recorded error-path fixture of the test suite enumerates every export of that ending, and a new
+ * one would change a fixture that must stay as it is.  It behaves as the `_device` calls do.  It
+ * runs a counter reset and seven launches on `stream` (classify, search, count, the split's three
+ * for the prefix sum, write) on handle scratch that grows with B: 36 bytes a segment -- a 32-byte
+ * record (piece count, flag, up to seven anchors as grid nodes) and a candidate entry -- for
+ * TGMS_MAX_SEGMENTS segments a trajectory, and 12 bytes more a trajectory, 588 in all, because S is
+ * not known on the host.  It returns TGMS_ERR_UNSUPPORTED while its
+ * stream is capturing and is ordered among the handle's other scratch users.  The search is a
+ * persistent grid of workgroups over the candidate list, each with its window's 16-bit distances in
+ * LDS.  On a multi handle it runs on device 0; on a host handle it returns TGMS_ERR_UNSUPPORTED.
+ * tgms_corridor_reroute_batch on a host handle computes on the calling thread from the same core
+ * (the search is a queue); on a GPU handle it does one upload, builds the table in the handle's
+ * workspace, launches, does one download and copies the first S' rows to the caller. */
+#define TGMS_RRT_DONE 1      /* the trajectory gained a segment */
+#define TGMS_RRT_FULL 2      /* the re-routed legs did not fit TGMS_MAX_SEGMENTS: copied whole */
+#define TGMS_RRT_BLOCKED 4   /* the segment's seed holds a non-free node */
+#define TGMS_RRT_OUTSIDE 8   /* the leg's own seed leaves the grid: kept whole */
+#define TGMS_RRT_WINDOW 32   /* the window holds more than TGMS_RRT_WINDOW_NODES nodes */
+#define TGMS_RRT_ENDS 64     /* an end node is not free, or a path node next to an anchor is not clear */
+#define TGMS_RRT_NOPATH 128  /* no path inside the window: grow margin */
+#define TGMS_RRT_LONG 256    /* the path needs more than max_pieces pieces */
+#define TGMS_RRT_WINDOW_NODES 32768
+/* TGMS_FEAS_NONFINITE (16) and TGMS_NEAR_NONE (-1) are reused */
+tgms_status tgms_corridor_reroute_batch_dev(tgms_handle* h, int32_t B, const int32_t* d_seg_offsets,
+                                            const double* d_waypoints /* [S+B][3] */,
+                                            const double* d_seg_times /* [S], nullable */,
+                                            const tgms_field* field /* host */, const int32_t* d_table,
+                                            int32_t margin, int32_t max_pieces,
+                                            int32_t* d_seg_offsets_out /* [B+1] */, double* d_waypoints_out,
+                                            double* d_seg_times_out /* nullable */, int32_t* d_parent /* nullable */,
+                                            int32_t* d_seg_flags_out /* nullable */,
+                                            int32_t* d_hops /* [S] per input segment, nullable */,
+                                            int64_t* d_totals /* [1]: S' */, int32_t* d_flags /* [B], nullable */,
+                                            void* stream);
+tgms_status tgms_corridor_reroute_batch(tgms_handle* h, int32_t B, const int32_t* seg_offsets,
+                                        const double* waypoints, const double* seg_times, const tgms_field* field,
+                                        const float* values, double r_free, int32_t margin, int32_t max_pieces,
+                                        int32_t* seg_offsets_out, double* waypoints_out, double* seg_times_out,
+                                        int32_t* parent, int32_t* seg_flags_out, int32_t* hops, int64_t* totals,
+                                        int32_t* flags);
+
 /* ---- distance-field build: exact Euclidean transform of a voxel map ----
  * Step zero of the map calls: the field that tgms_field_clearance_batch_device,
  * tgms_field_occupancy_device and through it the inflation and the subdivision start from, made

@@ -28,6 +28,10 @@ FLD_UNRESOLVED = 64  # tgms_field_clearance_batch: the row spent max_evals; only
 INF_BLOCKED, INF_OUTSIDE, INF_CAPPED = 1, 2, 4  # tgms_corridor_inflate_batch, with FEAS_NONFINITE
 SUB_DONE, SUB_FULL, SUB_BLOCKED, SUB_OUTSIDE = 1, 2, 4, 8  # tgms_corridor_subdivide_batch, with FEAS_NONFINITE
 SUB_MAX_DEPTH = 4  # sixteenths of a leg
+# tgms_corridor_reroute_batch, with FEAS_NONFINITE
+RRT_DONE, RRT_FULL, RRT_BLOCKED, RRT_OUTSIDE, RRT_WINDOW, RRT_ENDS, RRT_NOPATH, RRT_LONG = 1, 2, 4, 8, 32, 64, 128, 256
+RRT_WINDOW_NODES = 32768  # the largest window the re-route searches
+RRT_MAX_PIECES = 8
 EDT_SIGNED = 1  # tgms_field_edt mode: negative inside, zero level half a spacing outside the occupied nodes
 EDT_NONE = 2**31 - 1  # the squared distance to an empty set
 THRUST_STRIDE = 6  # f_min t_fmin f_max t_fmax tilt_max t_tilt
@@ -59,6 +63,7 @@ EXPORTS = [
     "tgms_field_clearance_batch", "tgms_field_clearance_batch_device",
     "tgms_field_occupancy_device", "tgms_corridor_inflate_batch", "tgms_corridor_inflate_batch_device",
     "tgms_corridor_subdivide_batch", "tgms_corridor_subdivide_batch_device",
+    "tgms_corridor_reroute_batch", "tgms_corridor_reroute_batch_dev",
     "tgms_field_edt_work_size", "tgms_field_edt_device", "tgms_field_edt",
     "tgms_thrust_batch", "tgms_thrust_batch_device",
     "tgms_rate_batch", "tgms_rate_batch_device",
@@ -234,6 +239,12 @@ def load(path: str = ""):
     L.tgms_corridor_subdivide_batch.argtypes = [vp, i32, vp, vp, vp, ctypes.POINTER(Field), vp, dbl, i32, vp, vp, vp, vp,
                                                 vp, vp, vp]
     L.tgms_corridor_subdivide_batch.restype = ctypes.c_int
+    L.tgms_corridor_reroute_batch_dev.argtypes = [vp, i32, vp, vp, vp, ctypes.POINTER(Field), vp, i32, i32, vp, vp, vp,
+                                                  vp, vp, vp, vp, vp, vp]
+    L.tgms_corridor_reroute_batch_dev.restype = ctypes.c_int
+    L.tgms_corridor_reroute_batch.argtypes = [vp, i32, vp, vp, vp, ctypes.POINTER(Field), vp, dbl, i32, i32, vp, vp, vp,
+                                              vp, vp, vp, vp, vp]
+    L.tgms_corridor_reroute_batch.restype = ctypes.c_int
     L.tgms_field_edt_work_size.argtypes = [ctypes.POINTER(Field), i32]
     L.tgms_field_edt_work_size.restype = ctypes.c_size_t
     L.tgms_field_edt_device.argtypes = [vp, ctypes.POINTER(Field), vp, dbl, i32, vp, vp, vp, vp]

@@ -58,6 +58,7 @@ struct tgms_handle {
     // (grow-only, ordered by scratch_ev)
     void* d_nbr_ws = nullptr;
     size_t nbr_ws_cap = 0;
+    bool reroute_ready = false;  // the re-route search's dynamic LDS limit is raised on this handle's device
     // ragged plans: the per-M group launches fork onto these streams and join back, so
     // the groups (each a few hundred wavefronts) run side by side instead of in series
     hipStream_t aux[TGMS_AUX_STREAMS] = {};

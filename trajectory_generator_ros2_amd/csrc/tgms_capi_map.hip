@@ -1,5 +1,5 @@
 // tgms_capi_map.hip — the voxel-map calls (include/tgms.h): field clearance, occupancy table,
-// corridor inflation and subdivision, distance-field build.
+// corridor inflation, subdivision and re-route, distance-field build.
 #include "tgms_capi.h"
 #include "tgms_host.h"
 
@@ -305,6 +305,110 @@ tgms_status tgms_corridor_subdivide_batch(tgms_handle* h, int32_t B, const int32
     out.take(oT, S1);
     out.take(oPar, S1);
     out.take(oSegFl, S1);
+    out.take(oFl, n);
+    return TGMS_OK;
+}
+
+// ---- corridor re-route: detour blocked legs through the free nodes of the map ----
+
+// What both re-route calls check before they look at a pointer to the batch.
+static tgms_status check_reroute(tgms_handle* h, int32_t B, const tgms_field* field, const void* map, int32_t margin,
+                                 int32_t max_pieces, const void* T, const void* so_out, const void* W_out,
+                                 const void* T_out, const void* totals) {
+    if (B < 0) return set_err(h, TGMS_ERR_INVALID_ARG, "bad B");
+    if (tgms_status s = check_inflate_field(h, field); s != TGMS_OK) return s;
+    if (!map) return set_err(h, TGMS_ERR_INVALID_ARG, "values or table NULL");
+    if (margin < 0) return set_err(h, TGMS_ERR_INVALID_ARG, "margin must be >= 0");
+    if (max_pieces < 2 || max_pieces > 8) return set_err(h, TGMS_ERR_INVALID_ARG, "max_pieces must be in 2..8");
+    if ((T == nullptr) != (T_out == nullptr))
+        return set_err(h, TGMS_ERR_INVALID_ARG, "seg_times and seg_times_out are NULL together or not at all");
+    if (!so_out || !totals) return set_err(h, TGMS_ERR_INVALID_ARG, "seg_offsets_out or totals is NULL");
+    if (B > 0 && !W_out) return set_err(h, TGMS_ERR_INVALID_ARG, "waypoints_out is NULL");
+    return TGMS_OK;
+}
+
+// The launch of either call, on the handle's scratch.
+static tgms_status run_reroute(tgms_handle* h, hipStream_t st, int32_t B, const int32_t* d_so, const double* dW,
+                               const double* dT, const tgms_field& field, const int32_t* d_table, int32_t margin,
+                               int32_t max_pieces, int32_t* d_so_out, double* dW_out, double* dT_out, int32_t* d_parent,
+                               int32_t* d_seg_flags, int32_t* d_hops, int64_t* d_totals, int32_t* d_flags) {
+    return launch_on_scratch(h, st, "tgms_corridor_reroute_batch_dev", "launch_reroute", tgms::reroute_scratch_bytes(B),
+                             [&](void* ws) {
+                                 if (!h->reroute_ready) {
+                                     if (const hipError_t e = tgms::reroute_prepare(); e != hipSuccess) return e;
+                                     h->reroute_ready = true;
+                                 }
+                                 return tgms::launch_reroute(B, d_so, dW, dT, field, d_table, margin, max_pieces, ws,
+                                                             d_so_out, dW_out, dT_out, d_parent, d_seg_flags, d_hops,
+                                                             d_totals, d_flags, st);
+                             });
+}
+
+tgms_status tgms_corridor_reroute_batch_dev(tgms_handle* h, int32_t B, const int32_t* d_so, const double* dW,
+                                            const double* dT, const tgms_field* field, const int32_t* d_table,
+                                            int32_t margin, int32_t max_pieces, int32_t* d_so_out, double* dW_out,
+                                            double* dT_out, int32_t* d_parent, int32_t* d_seg_flags, int32_t* d_hops,
+                                            int64_t* d_totals, int32_t* d_flags, void* stream) {
+    if (tgms_status e = enter(h, __func__); e != TGMS_OK) return e;
+    const tgms_status s = check_reroute(h, B, field, d_table, margin, max_pieces, dT, d_so_out, dW_out, dT_out, d_totals);
+    if (s != TGMS_OK) return s;
+    if (B > 0 && (!d_so || !dW)) return set_err(h, TGMS_ERR_INVALID_ARG, "NULL device pointer");
+    TGMS_CHECK_ALIGNED(h, dW, dT, dW_out, dT_out, d_totals);
+    return run_reroute(h, static_cast<hipStream_t>(stream), B, d_so, dW, dT, *field, d_table, margin, max_pieces, d_so_out,
+                       dW_out, dT_out, d_parent, d_seg_flags, d_hops, d_totals, d_flags);
+}
+
+tgms_status tgms_corridor_reroute_batch(tgms_handle* h, int32_t B, const int32_t* so, const double* waypoints,
+                                        const double* seg_times, const tgms_field* field, const float* values,
+                                        double r_free, int32_t margin, int32_t max_pieces, int32_t* so_out,
+                                        double* waypoints_out, double* seg_times_out, int32_t* parent,
+                                        int32_t* seg_flags_out, int32_t* hops, int64_t* totals, int32_t* flags) {
+    if (tgms_status e = enter(h); e != TGMS_OK) return e;
+    tgms_status s = check_offsets(h, B, so, TGMS_MAX_SEGMENTS, nullptr, nullptr);
+    if (s != TGMS_OK) return s;
+    s = check_reroute(h, B, field, values, margin, max_pieces, seg_times, so_out, waypoints_out, seg_times_out, totals);
+    if (s != TGMS_OK) return s;
+    if (!std::isfinite(r_free)) return set_err(h, TGMS_ERR_INVALID_ARG, "r_free must be finite");
+    if (B == 0) {
+        so_out[0] = 0;
+        totals[0] = 0;
+        return TGMS_OK;
+    }
+    if (!waypoints) return set_err(h, TGMS_ERR_INVALID_ARG, "NULL pointer");
+    if (h->host) {
+        tgms::host::reroute(B, so, waypoints, seg_times, *field, values, r_free, margin, max_pieces, so_out, waypoints_out,
+                            seg_times_out, parent, seg_flags_out, hops, totals, flags);
+        return TGMS_OK;
+    }
+    // the map goes up with the batch and its table is built beside them, in the workspace; the
+    // outputs at the capacity of the header, of which the first S' rows go to the caller
+    const size_t S = (size_t)so[B], n = (size_t)B;
+    const size_t cap = std::min(S * (size_t)max_pieces, (size_t)TGMS_MAX_SEGMENTS * n);
+    const size_t N = (size_t)field->n[0] * field->n[1] * field->n[2];
+    Outputs out;
+    const auto oW = out.add(waypoints_out, (cap + n) * 3), oT = out.add(seg_times_out, cap);
+    const auto oTot = out.add(totals, 1);
+    const auto oSo = out.add(so_out, n + 1), oPar = out.add(parent, cap), oSegFl = out.add(seg_flags_out, cap),
+               oHops = out.add(hops, S), oFl = out.add(flags, n);
+    double *dW, *dT;
+    float* dV;
+    int32_t *dSo, *dTab;
+    s = stage(h, {input(&dW, waypoints, (S + n) * 3), input(&dT, seg_times, S), input(&dV, values, N),
+                  input(&dSo, so, n + 1), output(&dTab, inflate_table_entries(*field)), output(&out)});
+    if (s != TGMS_OK) return s;
+    TGMS_HIP(h, tgms::launch_field_occupancy(*field, dV, r_free, dTab, h->stream));
+    s = run_reroute(h, h->stream, B, dSo, dW, dT, *field, dTab, margin, max_pieces, out.dev(oSo), out.dev(oW), out.dev(oT),
+                    out.dev(oPar), out.dev(oSegFl), out.dev(oHops), out.dev(oTot), out.dev(oFl));
+    if (s == TGMS_OK) s = out.fetch(h);
+    if (s != TGMS_OK) return s;
+    out.take(oTot, 1);
+    const size_t S1 = (size_t)totals[0];
+    out.take(oSo, n + 1);
+    out.take(oW, (S1 + n) * 3);
+    out.take(oT, S1);
+    out.take(oPar, S1);
+    out.take(oSegFl, S1);
+    out.take(oHops, S);
     out.take(oFl, n);
     return TGMS_OK;
 }

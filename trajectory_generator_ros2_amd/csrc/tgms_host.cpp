@@ -36,6 +36,7 @@
 #include "tgms_inflate_core.h"
 #include "tgms_neighbors_core.h"
 #include "tgms_separation_core.h"
+#include "tgms_reroute_core.h"
 #include "tgms_subdivide_core.h"
 #include "tgms_rate_core.h"
 #include "tgms_thrust_core.h"
@@ -801,6 +802,148 @@ void subdivide(int32_t B, const int32_t* so, const double* W, const double* T, c
                 if (T_out) T_out[out] = sub::leaf_time(T[s0 + i], i1 - i0);
                 if (parent) parent[out] = (int32_t)(s0 + i);
                 if (seg_flags) seg_flags[out] = sub::leaf_flag(word, i0);
+            }
+            if (i == M - 1) std::copy(w + 3, w + 6, W_out + (out + b) * 3);
+        }
+        if (flags) flags[b] = all;
+    }
+    so_out[B] = (int32_t)out;
+    totals[0] = out;
+}
+
+namespace {
+
+// One leg of the re-route: its record and its hop count.  dist and queue are the caller's, reused.
+void reroute_leg(const tgms::inflate::Grid& g, const int32_t* table, const double (&w0)[3], const double (&w1)[3],
+                 int32_t margin, int max_pieces, tgms::reroute::Record& rec, int32_t& hops, std::vector<uint16_t>& dist,
+                 std::vector<int32_t>& queue) {
+    namespace rr = tgms::reroute;
+    hops = TGMS_NEAR_NONE;
+    int32_t lo[3], hi[3];
+    const int32_t fl = rr::classify(g, table, w0, w1, lo, hi);
+    rec.head = rr::pack_head(1, fl < 0 ? TGMS_RRT_BLOCKED : fl);
+    if (fl >= 0) return;
+    auto keep = [&](int32_t why) { rec.head = rr::pack_head(1, TGMS_RRT_BLOCKED | why); };
+    const rr::Window w = rr::window(g, lo, hi, margin);
+    if (w.nodes > rr::WINDOW_NODES) return keep(TGMS_RRT_WINDOW);
+    int32_t A[3], Z[3];
+    for (int a = 0; a < 3; ++a) {
+        A[a] = rr::nearest(g.o[a], g.h, w0[a], lo[a], hi[a]);
+        Z[a] = rr::nearest(g.o[a], g.h, w1[a], lo[a], hi[a]);
+    }
+    if (!rr::node_free(g, table, A[0], A[1], A[2]) || !rr::node_free(g, table, Z[0], Z[1], Z[2]))
+        return keep(TGMS_RRT_ENDS);
+    // the search: a queue from Z, until A has its distance
+    dist.assign((size_t)w.nodes, rr::D_UNREACHED);
+    for (int32_t z = 0; z < w.n[2]; ++z)
+        for (int32_t y = 0; y < w.n[1]; ++y)
+            for (int32_t x = 0; x < w.n[0]; ++x)
+                if (!rr::node_free(g, table, w.lo[0] + x, w.lo[1] + y, w.lo[2] + z))
+                    dist[(size_t)rr::window_index(w, x, y, z)] = rr::D_NOT_FREE;
+    const int32_t qa = rr::window_index(w, A[0] - w.lo[0], A[1] - w.lo[1], A[2] - w.lo[2]);
+    const int32_t qz = rr::window_index(w, Z[0] - w.lo[0], Z[1] - w.lo[1], Z[2] - w.lo[2]);
+    queue.clear();
+    queue.push_back(qz);
+    dist[(size_t)qz] = 0;
+    for (size_t head = 0; head < queue.size() && dist[(size_t)qa] == rr::D_UNREACHED; ++head) {
+        const int32_t q = queue[head], x = q % w.n[0], y = (q / w.n[0]) % w.n[1], z = q / (w.n[0] * w.n[1]);
+        for (int d = 0; d < 6; ++d) {
+            int32_t nx, ny, nz;
+            if (!rr::neighbour(w, x, y, z, d, nx, ny, nz)) continue;
+            const int32_t qi = rr::window_index(w, nx, ny, nz);
+            if (dist[(size_t)qi] != rr::D_UNREACHED) continue;
+            dist[(size_t)qi] = (uint16_t)(dist[(size_t)q] + 1);
+            queue.push_back(qi);
+        }
+    }
+    if (dist[(size_t)qa] == rr::D_UNREACHED) return keep(TGMS_RRT_NOPATH);
+    hops = dist[(size_t)qa];
+    // the targets: the path nodes first .. last, then w1; the descent runs beside the greedy
+    double pt[3];
+    rr::node_point(g, rr::node_id(g, A[0], A[1], A[2]), pt);
+    const int first = rr::same_point(pt, w0) ? 1 : 0;
+    rr::node_point(g, rr::node_id(g, Z[0], Z[1], Z[2]), pt);
+    const int last = hops - (rr::same_point(pt, w1) ? 1 : 0);
+    const int n = std::max(0, last - first + 1) + 1;
+    int32_t cur[3] = {A[0] - w.lo[0], A[1] - w.lo[1], A[2] - w.lo[2]};
+    int pos = 0, anchor = -1, anchors = 0;
+    double qanchor[3] = {w0[0], w0[1], w0[2]}, prev[3] = {w0[0], w0[1], w0[2]};
+    int32_t prev_id = TGMS_NEAR_NONE;
+    for (int t = 0; t < n; ++t) {
+        int32_t id = TGMS_NEAR_NONE;
+        if (t < n - 1) {
+            while (pos < first + t) {  // one step of the descent
+                const int want = (int)dist[(size_t)rr::window_index(w, cur[0], cur[1], cur[2])] - 1;
+                for (int d = 0; d < 6; ++d) {
+                    int32_t nx, ny, nz;
+                    if (!rr::neighbour(w, cur[0], cur[1], cur[2], d, nx, ny, nz)) continue;
+                    if ((int)dist[(size_t)rr::window_index(w, nx, ny, nz)] != want) continue;
+                    cur[0] = nx, cur[1] = ny, cur[2] = nz;
+                    break;
+                }
+                ++pos;
+            }
+            id = rr::node_id(g, w.lo[0] + cur[0], w.lo[1] + cur[1], w.lo[2] + cur[2]);
+            rr::node_point(g, id, pt);
+        } else {
+            std::copy(w1, w1 + 3, pt);
+        }
+        while (!rr::clear_points(g, table, qanchor, pt)) {
+            if (const int32_t why = rr::on_fail(anchor, t, anchors, max_pieces)) return keep(why);
+            rec.anchor[anchors++] = prev_id;
+            anchor = t - 1;
+            std::copy(prev, prev + 3, qanchor);
+        }
+        std::copy(pt, pt + 3, prev);
+        prev_id = id;
+    }
+    rec.head = rr::pack_head(anchors + 1, 0);
+}
+
+}  // namespace
+
+void reroute(int32_t B, const int32_t* so, const double* W, const double* T, const tgms_field& fld, const float* values,
+             double r_free, int32_t margin, int32_t max_pieces, int32_t* so_out, double* W_out, double* T_out,
+             int32_t* parent, int32_t* seg_flags, int32_t* hops, int64_t* totals, int32_t* flags) {
+    namespace inf = tgms::inflate;
+    namespace rr = tgms::reroute;
+    const inf::Grid g = inf::make_grid(fld);
+    std::vector<int32_t> table((size_t)(fld.n[0] + 1) * (fld.n[1] + 1) * (fld.n[2] + 1));
+    field_occupancy(fld, values, r_free, table.data());
+    std::vector<uint16_t> dist;
+    std::vector<int32_t> queue;
+    int64_t out = 0;
+    for (int32_t b = 0; b < B; ++b) {
+        const int64_t s0 = so[b];
+        const int M = so[b + 1] - so[b];
+        rr::Record rec[TGMS_MAX_SEGMENTS];
+        int sum = 0;
+        for (int i = 0; i < M; ++i) {
+            const double* w = W + (s0 + i + b) * 3;
+            const double w0[3] = {w[0], w[1], w[2]}, w1[3] = {w[3], w[4], w[5]};
+            int32_t hp;
+            reroute_leg(g, table.data(), w0, w1, margin, max_pieces, rec[i], hp, dist, queue);
+            if (hops) hops[s0 + i] = hp;
+            sum += rr::head_pieces(rec[i].head);
+        }
+        const bool full = sum > TGMS_MAX_SEGMENTS;
+        int32_t all = full ? TGMS_RRT_FULL : (sum > M ? TGMS_RRT_DONE : 0);
+        so_out[b] = (int32_t)out;
+        for (int i = 0; i < M; ++i) {
+            const double* w = W + (s0 + i + b) * 3;
+            const double w0[3] = {w[0], w[1], w[2]}, w1[3] = {w[3], w[4], w[5]};
+            const int p = full ? 1 : rr::head_pieces(rec[i].head);
+            const double leg = p > 1 ? rr::length(w0, w1) : 0.0;
+            for (int q = 0; q < p; ++q, ++out) {
+                double a[3] = {w0[0], w0[1], w0[2]}, e[3] = {w1[0], w1[1], w1[2]};
+                if (q > 0) rr::node_point(g, rec[i].anchor[q - 1], a);
+                if (q < p - 1) rr::node_point(g, rec[i].anchor[q], e);
+                std::copy(a, a + 3, W_out + (out + b) * 3);
+                if (T_out) T_out[out] = p > 1 ? rr::piece_time(T[s0 + i], rr::length(a, e), leg) : T[s0 + i];
+                if (parent) parent[out] = (int32_t)(s0 + i);
+                const int32_t fl = p > 1 ? 0 : rr::kept_flag(rec[i].head, full);
+                all |= fl;
+                if (seg_flags) seg_flags[out] = fl;
             }
             if (i == M - 1) std::copy(w + 3, w + 6, W_out + (out + b) * 3);
         }

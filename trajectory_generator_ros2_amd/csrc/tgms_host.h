@@ -108,6 +108,14 @@ void subdivide(int32_t B, const int32_t* so, const double* W, const double* T, c
                const float* values, double r_free, int32_t max_depth, int32_t* so_out, double* W_out, double* T_out,
                int32_t* parent, int32_t* seg_flags, int64_t* totals, int32_t* flags);
 
+// The corridor re-route (include/tgms.h tgms_corridor_reroute_batch) of a whole batch, trajectory
+// by trajectory: the table first, then per candidate leg a queue search of its window, the descent
+// and the greedy of tgms_reroute_core.h, the trajectory's budget and its rows.  The offsets are
+// valid; T and T_out are nullable together, parent, seg_flags, hops and flags nullable.
+void reroute(int32_t B, const int32_t* so, const double* W, const double* T, const tgms_field& field,
+             const float* values, double r_free, int32_t margin, int32_t max_pieces, int32_t* so_out, double* W_out,
+             double* T_out, int32_t* parent, int32_t* seg_flags, int32_t* hops, int64_t* totals, int32_t* flags);
+
 // The corridor containment (include/tgms.h tgms_corridor_batch) of a whole batch, trajectory by
 // trajectory: per segment and face the item of tgms_corridor_core.h, the segment's fold in face
 // order, the trajectory's fold left to right.  face_offsets NULL: all F faces apply to every

@@ -273,4 +273,19 @@ hipError_t launch_subdivide(int32_t B, const int32_t* seg_offsets, const double*
                             const tgms_field& fld, const int32_t* table, int32_t max_depth, void* scratch,
                             int32_t* so_out, double* W_out, double* T_out, int32_t* parent, int32_t* seg_flags,
                             int64_t* totals, int32_t* flags, hipStream_t stream);
+
+// Corridor re-route (tgms_reroute.hip): the legs whose own lattice box holds a non-free node of
+// `table` detoured through the free nodes of a window of the map; the new offsets, waypoints,
+// times (T and T_out nullable together), parent rows, segment flags, hops per input segment (all
+// three nullable), totals [1] = S' and flags [B] (nullable).  A counter reset and seven launches on
+// `stream`: classify, the persistent search, count, launch_count_scan, the write; `scratch` holds
+// reroute_scratch_bytes(B) bytes, 256-byte aligned.  reroute_prepare raises the search kernel's
+// dynamic LDS limit on the current device, once before the first launch there.  B == 0 writes
+// so_out[0] and the total.
+size_t reroute_scratch_bytes(int32_t B);
+hipError_t reroute_prepare();
+hipError_t launch_reroute(int32_t B, const int32_t* seg_offsets, const double* W, const double* T, const tgms_field& fld,
+                          const int32_t* table, int32_t margin, int32_t max_pieces, void* scratch, int32_t* so_out,
+                          double* W_out, double* T_out, int32_t* parent, int32_t* seg_flags, int32_t* hops,
+                          int64_t* totals, int32_t* flags, hipStream_t stream);
 }  // namespace tgms

@@ -430,6 +430,36 @@ class Solver:
         S2 = int(totals[0])
         return so2, W2[:S2 + B], None if T2 is None else T2[:S2], parent[:S2], seg_flags[:S2], flags
 
+    def corridor_reroute(self, seg_offsets, waypoints, origin, h: float, values, r_free: float, margin: int,
+                         max_pieces: int = _lib.RRT_MAX_PIECES, seg_times=None):
+        """Corridor re-route (include/tgms.h tgms_corridor_reroute_batch): every leg whose own lattice
+        bounding box holds a non-free node of the voxel field `values` [nz,ny,nx] is replaced by a
+        shortest 6-neighbour path through the free nodes of its box widened by `margin` nodes, reduced
+        to at most max_pieces pieces with free boxes.  Returns the new batch trimmed to its S' segments:
+        (seg_offsets' [B+1], waypoints' [S'+B,3], seg_times' [S'] (None without seg_times), parent
+        [S'], seg_flags [S'], hops [S] per input segment (NEAR_NONE: not searched or no path) and
+        flags [B] of RRT_* bits and FEAS_NONFINITE)."""
+        so, W, T, _, _ = _csr(seg_offsets, waypoints, seg_times)
+        v = np.ascontiguousarray(values, dtype=np.float32)
+        assert v.ndim == 3, "values must be [nz, ny, nx]"
+        fld = _lib.Field(origin, h, v.shape[::-1])
+        B = so.shape[0] - 1
+        S = int(so[-1]) if B > 0 else 0
+        cap = min(S * max(2, min(int(max_pieces), _lib.RRT_MAX_PIECES)), _lib.MAX_SEGMENTS * B)
+        so2 = np.zeros(B + 1, dtype=np.int32)
+        W2 = np.zeros((cap + B, 3), dtype=np.float64)
+        T2 = None if T is None else np.zeros(cap, dtype=np.float64)
+        parent, seg_flags = np.zeros(cap, dtype=np.int32), np.zeros(cap, dtype=np.int32)
+        hops = np.zeros(S, dtype=np.int32)
+        totals = np.zeros(1, dtype=np.int64)
+        flags = np.zeros(B, dtype=np.int32)
+        self._check(self._L.tgms_corridor_reroute_batch(
+            self._h, B, _ptr(so), _ptr(W), _ptr(T), ctypes.byref(fld), _ptr(v), float(r_free), int(margin),
+            int(max_pieces), _ptr(so2), _ptr(W2), _ptr(T2), _ptr(parent), _ptr(seg_flags), _ptr(hops), _ptr(totals),
+            _ptr(flags)))
+        S2 = int(totals[0])
+        return so2, W2[:S2 + B], None if T2 is None else T2[:S2], parent[:S2], seg_flags[:S2], hops, flags
+
     def field_edt(self, occ, origin, h: float, max_dist: float, signed: bool = False):
         """Distance-field build (include/tgms.h tgms_field_edt): the exact Euclidean distance
         transform of the occupancy grid `occ` [nz,ny,nx] (uint8, occupied where not 0; node (0,0,0) at
@@ -453,15 +483,24 @@ class Solver:
         return int(self._L.tgms_field_edt_work_size(ctypes.byref(fld), _lib.EDT_SIGNED if signed else 0))
 
     def corridor_from_map(self, seg_offsets, waypoints, seg_times, origin, h: float, values, r_free: float,
-                          max_grow: int, max_depth: int = _lib.SUB_MAX_DEPTH):
+                          max_grow: int, max_depth: int = _lib.SUB_MAX_DEPTH, reroute=None):
         """From a voxel map to what corridor_loop() takes, on host arrays: corridor_subdivide, then
         corridor_inflate on its output.  Returns ((seg_offsets, waypoints, seg_times, faces,
         face_offsets), (sub_flags [B], sub_seg_flags [S'], inf_seg_flags [S'], inf_flags [B])); a
-        segment with SUB_BLOCKED is the one with INF_BLOCKED and needs re-routing."""
+        segment with SUB_BLOCKED is the one with INF_BLOCKED and needs re-routing.  reroute = (margin,
+        max_pieces): corridor_reroute runs between the two; the batch and the inflation flags are those
+        of its output (the subdivision's segment flags stay those of the subdivision's S' rows) and the
+        second tuple gains (rrt_flags [B], rrt_seg_flags [S''], rrt_parent [S''], rrt_hops [S'])."""
         so, W, T, _, sub_seg, sub_fl = self.corridor_subdivide(seg_offsets, waypoints, origin, h, values, r_free,
                                                                max_depth, seg_times)
+        rrt = ()
+        if reroute is not None:
+            margin, max_pieces = reroute
+            so, W, T, rrt_par, rrt_seg, rrt_hops, rrt_fl = self.corridor_reroute(so, W, origin, h, values, r_free,
+                                                                                 margin, max_pieces, T)
+            rrt = (rrt_fl, rrt_seg, rrt_par, rrt_hops)
         _, faces, fo, inf_seg, inf_fl = self.corridor_inflate(so, W, origin, h, values, r_free, max_grow)
-        return (so, W, T, faces, fo), (sub_fl, sub_seg, inf_seg, inf_fl)
+        return (so, W, T, faces, fo), (sub_fl, sub_seg, inf_seg, inf_fl) + rrt
 
     def refine(self, seg_offsets, waypoints, seg_times, end_derivs=None, k_T: float = 1.0, eta: float = 0.1,
                iters: int = 10, coeffs: bool = True):
@@ -721,6 +760,23 @@ class Solver:
             self._h, int(B), _ptr(d_seg_offsets), _ptr(d_waypoints), _ptr(d_seg_times), ctypes.byref(fld),
             _ptr(d_table), int(max_depth), _ptr(d_seg_offsets_out), _ptr(d_waypoints_out), _ptr(d_seg_times_out),
             _ptr(d_parent), _ptr(d_seg_flags_out), _ptr(d_totals), _ptr(d_flags), ctypes.c_void_p(stream)))
+
+
+    def corridor_reroute_device(self, B: int, d_seg_offsets, d_waypoints, origin, h: float, n, d_table, margin: int,
+                                max_pieces: int, d_seg_offsets_out, d_waypoints_out, d_totals, d_seg_times=None,
+                                d_seg_times_out=None, d_parent=None, d_seg_flags_out=None, d_hops=None, d_flags=None,
+                                stream: int = 0) -> None:
+        """tgms_corridor_reroute_batch_dev: d_table of field_occupancy_device for the same grid; outputs
+        at the capacity cap = min(max_pieces S, MAX_SEGMENTS B): d_seg_offsets_out [B+1] int32,
+        d_waypoints_out [cap+B,3], d_seg_times_out [cap] (with d_seg_times, or neither), d_parent and
+        d_seg_flags_out [cap] int32, d_hops [S] int32 per input segment, d_totals [1] int64 = S', d_flags
+        [B] int32.  Not capturable: it grows handle scratch with B."""
+        fld = _lib.Field(origin, h, n)
+        self._check(self._L.tgms_corridor_reroute_batch_dev(
+            self._h, int(B), _ptr(d_seg_offsets), _ptr(d_waypoints), _ptr(d_seg_times), ctypes.byref(fld),
+            _ptr(d_table), int(margin), int(max_pieces), _ptr(d_seg_offsets_out), _ptr(d_waypoints_out),
+            _ptr(d_seg_times_out), _ptr(d_parent), _ptr(d_seg_flags_out), _ptr(d_hops), _ptr(d_totals), _ptr(d_flags),
+            ctypes.c_void_p(stream)))
 
 
 def sample_count(total_T: float, dt: float) -> int:
