@@ -1364,6 +1364,133 @@ tgms_status tgms_field_edt_device(tgms_handle* h, const tgms_field* field /* hos
 tgms_status tgms_field_edt(tgms_handle* h, const tgms_field* field, const uint8_t* occ, double max_dist, int32_t mode,
                            float* values, int32_t* d2);
 
+/* ---- waypoint repair: move map-blocked waypoints to the nearest free node ----
+ * What the re-route asks of the planner when it reports TGMS_RRT_ENDS: the waypoint itself sits in
+ * a cell with a non-free node, and no detour can fix a waypoint.  Two calls.  The first makes, per
+ * map and r_free like the occupancy table, the nearest free node of every node: the argument of the
+ * distance transform (a feature transform), not only its value.  The second moves every blocked
+ * waypoint of a batch onto the free node nearest to it and rescales the times of the legs it
+ * touched.  The results are integers and doubles with stated rounding: the host backend, the device
+ * and a brute-force search over all pairs of nodes agree to the bit.
+ *
+ * The nearest-free map.
+ *   Free node.  values[node] >= (float)r_free in fp32; NaN is not free: the occupancy call's rule.
+ *   Site of a node p.  Among the free nodes q with D = sum_a (p_a - q_a)^2 <= max_shift^2, in
+ * lattice units, the one with the least D; among equal D the lowest k, then the lowest j, then the
+ * lowest i, which is the lowest linear index (k ny + j) nx + i.  d_nearest[p] is that linear index,
+ * d_dsq[p] is D; both are TGMS_NEAR_NONE when there is no such node.  A free node is its own site
+ * with D = 0.  The tie order is the one a separable transform produces (tgms_repair_core.h has the
+ * argument), so an implementation may search a window of max_shift nodes per axis or whole lines,
+ * and the result does not depend on which.
+ *   max_shift lies in 1..32,768.  The grid rules are the distance-field build's: 2..16,384 nodes
+ * per axis, nx ny nz <= 2^31 - 1.
+ *   d_nearest [nz][ny][nx] int32 is required, d_dsq of the same shape is nullable.  d_work holds
+ * tgms_field_nearest_free_work_size bytes (one int32 per node: the middle pass), is caller-owned,
+ * 4-byte aligned and may be reused once the call's work on `stream` is done.  The outputs and the
+ * workspace must not overlap each other or the values.
+ *   TGMS_ERR_INVALID_ARG: the grid rules above; h or an origin component not finite; h <= 0; r_free
+ * not finite; max_shift outside 1..32,768; a NULL field, d_values, d_nearest or d_work; a buffer
+ * that is not 4-byte aligned.  The work size is 0 for a field the call would refuse.
+ *   tgms_field_nearest_free_dev uses no handle scratch and no host plan and may be captured into a
+ * HIP graph (three launches).  On a multi handle it runs on device 0; on a host handle it returns
+ * TGMS_ERR_UNSUPPORTED and tgms_field_nearest_free computes on the calling thread from the same
+ * core.  On a GPU handle tgms_field_nearest_free uploads the values, runs with a workspace from the
+ * handle and downloads: for tests and tools.
+ *
+ * The repair.  seg_offsets do not change: no segment is added.  Waypoint w is row s + b of
+ * trajectory b, as everywhere.
+ *   Own seed.  The inflation's seed rule applied to the pair (w, w): per axis lo = floor((w_a -
+ * origin_a) / h) with its corrective step, hi = ceil of the same with its own: one or two nodes an
+ * axis, the corners of the waypoint's cell.
+ *   Outcome, exactly one per waypoint, decided in this order.  A coordinate is not finite:
+ * TGMS_FEAS_NONFINITE.  The seed leaves the grid: TGMS_RPR_OUTSIDE.  Every node of the seed has
+ * d_nearest[node] == node (it is free): the waypoint is clear, flag 0.  `mode` protects it:
+ * TGMS_RPR_KEPT; TGMS_RPR_KEEP_FIRST protects a trajectory's first waypoint (where the vehicle is),
+ * TGMS_RPR_KEEP_LAST its last (where it must go).  Otherwise the waypoint is blocked and becomes
+ * TGMS_RPR_MOVED or TGMS_RPR_STUCK as below.  In every case but TGMS_RPR_MOVED the row is copied
+ * bit for bit.
+ *   Nearest node.  N(w)_a = floor((w_a - origin_a) / h + 0.5), each operation a separately rounded
+ * IEEE fp64 operation, no fused multiply-add, clamped to the grid: the re-route's end-node rule.
+ *   Move.  q = d_nearest[N(w)].  TGMS_NEAR_NONE: TGMS_RPR_STUCK, the row is copied; the caller
+ * grows max_shift.  Otherwise w'_a = origin_a + h q_a per axis, the product and the sum each
+ * rounded (the re-route's point rule), and the flag is TGMS_RPR_MOVED.  d_shift is sum_a (N(w)_a -
+ * q_a)^2 for a moved waypoint and TGMS_NEAR_NONE for every other.  A blocked waypoint whose nearest
+ * node is free snaps onto it with shift 0.
+ *   Times (d_seg_times and d_seg_times_out are NULL together or not at all).  len is the
+ * re-route's: sqrt((dx dx + dy dy) + dz dz), every operation rounded once.  A leg with at least one
+ * moved end gets T_s (len(w0', w1') / len(w0, w1)), quotient and product each rounded once, when
+ * both lengths are finite and positive; otherwise, and for every untouched leg, the time is copied
+ * bit for bit.
+ *   Outputs.  d_waypoints_out [S+B][3] (required), d_seg_times_out [S], d_wp_flags [S+B], d_shift
+ * [S+B] and d_flags [B], the OR of the trajectory's waypoint flags; all but the first nullable.
+ * Outputs must not overlap inputs.  A segment count outside 1..TGMS_MAX_SEGMENTS follows the
+ * inflation's rule: nothing is read for the trajectory, its rows are not written, and d_flags[b] =
+ * TGMS_FEAS_NONFINITE.
+ *   Guarantees.  (1) A moved waypoint lies on a free node.  (2) No ENDS after a full repair.  When
+ * the lattice arithmetic is exact -- origin + h i and (x - origin) / h carry no rounding, for
+ * instance a dyadic origin, h and waypoints -- and both waypoints of a leg are clear or
+ * TGMS_RPR_MOVED, tgms_corridor_reroute_batch with the same map and r_free never reports
+ * TGMS_RRT_ENDS for the leg.  The reasoning.  The re-route sets ENDS in two places.  First, an end
+ * node A or Z is not free.  A moved waypoint is a free node and its own nearest node.  The nearest
+ * node of a clear waypoint is a corner of its cell, hence of its own seed, all of whose nodes are
+ * free; the re-route clamps to the leg's seed, which contains the waypoint's, so the clamp changes
+ * nothing.  Second, the greedy fails at j = a + 1: the seed of an anchor and the very next point
+ * holds a non-free node.  From the anchor Q_0 = w0 the next point is Q_1, the point of A, unless it
+ * equals Q_0 and is dropped.  For a moved w0, or a clear one that lies on A, it does and is: the
+ * next point is then the point of the second path node, a free 6-neighbour of A, and the seed of
+ * two neighbouring free nodes is those two nodes.  Any other clear w0 has the seed of (w0, Q_1)
+ * inside its own cell, all free.  Every
+ * later anchor is a path node, Q_(j-1) of an earlier step, and the point after it is the next path
+ * node, again a free neighbour, or w1 itself after the last path node Z: the seed of (Z, w1) lies
+ * inside w1's cell when w1 is clear and is the node Z when w1 was moved (w1 = the point of Z, and
+ * that point was then dropped as the last-but-one).  So no test at j = a + 1 can fail.  WINDOW,
+ * NOPATH and LONG remain possible: they are about the space between the waypoints.  (3) A clear
+ * waypoint is never touched.  (4) No result depends on the launch shape, and a repeated call gives
+ * the same bits.
+ *   The limit.  The nearest free node is nearest in the lattice, not reachable: with a large
+ * max_shift a waypoint may land across a thin wall.  The caller bounds that with max_shift; a wall
+ * thicker than max_shift spacings cannot be crossed.
+ *   TGMS_ERR_INVALID_ARG: the grid rules above; unknown mode bits; a NULL input or d_waypoints_out;
+ * exactly one of the two time arrays NULL; an fp64 array that is not 16-byte aligned; in the
+ * host-pointer call also r_free not finite and max_shift out of range.  B == 0 is TGMS_OK and
+ * launches nothing.
+ *   The device entry points end in `_dev` -- deliberately not `_device`, for the re-route's reason:
+ * the recorded error-path fixture of the test suite enumerates every export of that ending and must
+ * stay as it is.  They behave as the `_device` calls do.  tgms_waypoints_repair_batch_dev is one
+ * launch, uses no handle scratch and may be captured; on a multi handle it runs on device 0; on a
+ * host handle it returns TGMS_ERR_UNSUPPORTED.  tgms_waypoints_repair_batch takes values, r_free
+ * and max_shift and builds the map itself: on a host handle on the calling thread from the same
+ * core, on a GPU handle with one upload, the map in the handle's workspace, and one download. */
+#define TGMS_RPR_MOVED 1      /* the waypoint was moved onto the site of its nearest node */
+#define TGMS_RPR_STUCK 2      /* blocked, and no free node within max_shift of its nearest node */
+#define TGMS_RPR_KEPT 4       /* blocked, but mode protects it */
+#define TGMS_RPR_OUTSIDE 8    /* the waypoint's own seed leaves the grid */
+#define TGMS_RPR_KEEP_FIRST 1 /* mode: never move a trajectory's first waypoint */
+#define TGMS_RPR_KEEP_LAST 2  /* mode: never move a trajectory's last waypoint */
+/* TGMS_FEAS_NONFINITE (16) and TGMS_NEAR_NONE (-1) are reused */
+size_t tgms_field_nearest_free_work_size(const tgms_field* field); /* bytes; 0 for a field the call refuses */
+tgms_status tgms_field_nearest_free_dev(tgms_handle* h, const tgms_field* field /* host */, const float* d_values,
+                                        double r_free, int32_t max_shift, int32_t* d_nearest /* [nz][ny][nx] */,
+                                        int32_t* d_dsq /* the same shape, nullable */,
+                                        void* d_work /* tgms_field_nearest_free_work_size bytes, caller-owned */,
+                                        void* stream);
+tgms_status tgms_field_nearest_free(tgms_handle* h, const tgms_field* field, const float* values, double r_free,
+                                    int32_t max_shift, int32_t* nearest, int32_t* dsq);
+tgms_status tgms_waypoints_repair_batch_dev(tgms_handle* h, int32_t B, const int32_t* d_seg_offsets,
+                                            const double* d_waypoints /* [S+B][3] */,
+                                            const double* d_seg_times /* [S], nullable */,
+                                            const tgms_field* field /* host */, const int32_t* d_nearest, int32_t mode,
+                                            double* d_waypoints_out /* [S+B][3] */,
+                                            double* d_seg_times_out /* [S], nullable */,
+                                            int32_t* d_wp_flags /* [S+B], nullable */,
+                                            int32_t* d_shift /* [S+B], nullable */, int32_t* d_flags /* [B], nullable */,
+                                            void* stream);
+tgms_status tgms_waypoints_repair_batch(tgms_handle* h, int32_t B, const int32_t* seg_offsets,
+                                        const double* waypoints, const double* seg_times, const tgms_field* field,
+                                        const float* values, double r_free, int32_t max_shift, int32_t mode,
+                                        double* waypoints_out, double* seg_times_out, int32_t* wp_flags, int32_t* shift,
+                                        int32_t* flags);
+
 /* ---- multi-GPU ----
  * One process drives devices 0 .. device_count-1 through one handle that owns one RCCL
  * communicator per device (ncclCommInitAll, rccl.h:236; RCCL is loaded here, not at

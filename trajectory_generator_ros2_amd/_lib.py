@@ -34,6 +34,10 @@ RRT_WINDOW_NODES = 32768  # the largest window the re-route searches
 RRT_MAX_PIECES = 8
 EDT_SIGNED = 1  # tgms_field_edt mode: negative inside, zero level half a spacing outside the occupied nodes
 EDT_NONE = 2**31 - 1  # the squared distance to an empty set
+# tgms_waypoints_repair_batch: waypoint flags, with FEAS_NONFINITE; the mode bits; shifts use NEAR_NONE
+RPR_MOVED, RPR_STUCK, RPR_KEPT, RPR_OUTSIDE = 1, 2, 4, 8
+RPR_KEEP_FIRST, RPR_KEEP_LAST = 1, 2
+RPR_MAX_SHIFT = 32768
 THRUST_STRIDE = 6  # f_min t_fmin f_max t_fmax tilt_max t_tilt
 THRUST_LOW, THRUST_HIGH, THRUST_TILT = 1, 2, 4  # with FEAS_NONFINITE
 RATE_STRIDE = 2  # omega_max t_omega
@@ -65,6 +69,8 @@ EXPORTS = [
     "tgms_corridor_subdivide_batch", "tgms_corridor_subdivide_batch_device",
     "tgms_corridor_reroute_batch", "tgms_corridor_reroute_batch_dev",
     "tgms_field_edt_work_size", "tgms_field_edt_device", "tgms_field_edt",
+    "tgms_field_nearest_free_work_size", "tgms_field_nearest_free_dev", "tgms_field_nearest_free",
+    "tgms_waypoints_repair_batch_dev", "tgms_waypoints_repair_batch",
     "tgms_thrust_batch", "tgms_thrust_batch_device",
     "tgms_rate_batch", "tgms_rate_batch_device",
     "tgms_dilate_batch", "tgms_dilate_batch_device",
@@ -251,6 +257,18 @@ def load(path: str = ""):
     L.tgms_field_edt_device.restype = ctypes.c_int
     L.tgms_field_edt.argtypes = [vp, ctypes.POINTER(Field), vp, dbl, i32, vp, vp]
     L.tgms_field_edt.restype = ctypes.c_int
+    L.tgms_field_nearest_free_work_size.argtypes = [ctypes.POINTER(Field)]
+    L.tgms_field_nearest_free_work_size.restype = ctypes.c_size_t
+    L.tgms_field_nearest_free_dev.argtypes = [vp, ctypes.POINTER(Field), vp, dbl, i32, vp, vp, vp, vp]
+    L.tgms_field_nearest_free_dev.restype = ctypes.c_int
+    L.tgms_field_nearest_free.argtypes = [vp, ctypes.POINTER(Field), vp, dbl, i32, vp, vp]
+    L.tgms_field_nearest_free.restype = ctypes.c_int
+    L.tgms_waypoints_repair_batch_dev.argtypes = [vp, i32, vp, vp, vp, ctypes.POINTER(Field), vp, i32, vp, vp, vp, vp,
+                                                  vp, vp]
+    L.tgms_waypoints_repair_batch_dev.restype = ctypes.c_int
+    L.tgms_waypoints_repair_batch.argtypes = [vp, i32, vp, vp, vp, ctypes.POINTER(Field), vp, dbl, i32, i32, vp, vp, vp,
+                                              vp, vp]
+    L.tgms_waypoints_repair_batch.restype = ctypes.c_int
     L.tgms_thrust_batch_device.argtypes = [vp, i32, vp, vp, vp, dbl, ctypes.POINTER(ThrustLimits), vp, vp, vp]
     L.tgms_thrust_batch_device.restype = ctypes.c_int
     L.tgms_thrust_batch.argtypes = [vp, i32, vp, vp, vp, dbl, ctypes.POINTER(ThrustLimits), vp, vp]

@@ -29,7 +29,7 @@ HIP_SOURCES = ["tgms_reduced.hip", "tgms_dense.hip", "tgms_band.hip", "tgms_samp
                "tgms_bounds.hip", "tgms_thrust.hip", "tgms_rate.hip", "tgms_dilate.hip", "tgms_corridor.hip",
                "tgms_corridor_split.hip", "tgms_cut.hip", "tgms_separation.hip", "tgms_neighbors.hip",
                "tgms_clearance.hip", "tgms_field.hip", "tgms_inflate.hip", "tgms_subdivide.hip", "tgms_reroute.hip",
-               "tgms_edt.hip", "tgms_capi.hip", "tgms_capi_multi.hip",
+               "tgms_edt.hip", "tgms_repair.hip", "tgms_capi.hip", "tgms_capi_multi.hip",
                "tgms_capi_analysis.hip", "tgms_capi_map.hip"]
 CXX_SOURCES = ["tgms_plan.cpp", "tgms_host.cpp"]  # host-only (no HIP): compiled by g++ into the same library
 HOST_SOURCES = ["MinSnap.cpp", "factory.cpp", "tgms_node_capi.cpp"]

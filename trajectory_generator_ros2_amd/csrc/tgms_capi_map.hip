@@ -1,5 +1,5 @@
 // tgms_capi_map.hip — the voxel-map calls (include/tgms.h): field clearance, occupancy table,
-// corridor inflation, subdivision and re-route, distance-field build.
+// corridor inflation, subdivision and re-route, distance-field build, waypoint repair.
 #include "tgms_capi.h"
 #include "tgms_host.h"
 
@@ -471,6 +471,129 @@ tgms_status tgms_field_edt(tgms_handle* h, const tgms_field* field, const uint8_
     if (s != TGMS_OK) return s;
     TGMS_HIP(h, tgms::launch_edt(*field, dOcc, max_dist, (mode & TGMS_EDT_SIGNED) != 0, out.dev(oVal), out.dev(oD2), dWork,
                                  h->stream));
+    return out.download(h);
+}
+
+// ---- waypoint repair: move map-blocked waypoints to the nearest free node ----
+
+// The grid, threshold and reach rules of the nearest-free map (include/tgms.h): the transform's
+// grid; `h` may be NULL (the work size).
+static tgms_status check_near_field(tgms_handle* h, const tgms_field* field) {
+    if (!field) return set_err(h, TGMS_ERR_INVALID_ARG, "field NULL");
+    return check_grid(h, field, kEdtGrid);
+}
+
+static tgms_status check_near(tgms_handle* h, const tgms_field* field, const void* values, double r_free,
+                              int32_t max_shift) {
+    if (tgms_status s = check_near_field(h, field); s != TGMS_OK) return s;
+    if (!std::isfinite(r_free)) return set_err(h, TGMS_ERR_INVALID_ARG, "r_free must be finite");
+    if (max_shift < 1 || max_shift > 32768) return set_err(h, TGMS_ERR_INVALID_ARG, "max_shift must be in 1..32,768");
+    if (!values) return set_err(h, TGMS_ERR_INVALID_ARG, "values NULL");
+    return TGMS_OK;
+}
+
+// What both repair calls check before they look at a pointer to the batch.
+static tgms_status check_repair(tgms_handle* h, int32_t B, const tgms_field* field, const void* map, int32_t mode,
+                                const void* T, const void* W_out, const void* T_out) {
+    if (B < 0) return set_err(h, TGMS_ERR_INVALID_ARG, "bad B");
+    if (tgms_status s = check_near_field(h, field); s != TGMS_OK) return s;
+    if (!map) return set_err(h, TGMS_ERR_INVALID_ARG, "values or nearest NULL");
+    if (mode & ~(TGMS_RPR_KEEP_FIRST | TGMS_RPR_KEEP_LAST)) return set_err(h, TGMS_ERR_INVALID_ARG, "unknown mode bits");
+    if ((T == nullptr) != (T_out == nullptr))
+        return set_err(h, TGMS_ERR_INVALID_ARG, "seg_times and seg_times_out are NULL together or not at all");
+    if (B > 0 && !W_out) return set_err(h, TGMS_ERR_INVALID_ARG, "waypoints_out is NULL");
+    return TGMS_OK;
+}
+
+size_t tgms_field_nearest_free_work_size(const tgms_field* field) {
+    return check_near_field(nullptr, field) == TGMS_OK ? tgms::nearest_free_work_bytes(*field) : 0;
+}
+
+tgms_status tgms_field_nearest_free_dev(tgms_handle* h, const tgms_field* field, const float* d_values, double r_free,
+                                        int32_t max_shift, int32_t* d_nearest, int32_t* d_dsq, void* d_work,
+                                        void* stream) {
+    if (tgms_status e = enter(h, __func__); e != TGMS_OK) return e;
+    if (tgms_status s = check_near(h, field, d_values, r_free, max_shift); s != TGMS_OK) return s;
+    if (!d_nearest || !d_work) return set_err(h, TGMS_ERR_INVALID_ARG, "nearest or workspace NULL");
+    if (misaligned({d_values, d_nearest, d_dsq, d_work}, 4))
+        return set_err(h, TGMS_ERR_INVALID_ARG, "4-byte device buffers must be 4-byte aligned");
+    TGMS_HIP(h, hipSetDevice(h->device));
+    TGMS_HIP(h, tgms::launch_nearest_free(*field, d_values, r_free, max_shift, d_nearest, d_dsq, d_work,
+                                          static_cast<hipStream_t>(stream)));
+    return TGMS_OK;
+}
+
+tgms_status tgms_field_nearest_free(tgms_handle* h, const tgms_field* field, const float* values, double r_free,
+                                    int32_t max_shift, int32_t* nearest, int32_t* dsq) {
+    if (tgms_status e = enter(h); e != TGMS_OK) return e;
+    if (tgms_status s = check_near(h, field, values, r_free, max_shift); s != TGMS_OK) return s;
+    if (!nearest) return set_err(h, TGMS_ERR_INVALID_ARG, "nearest NULL");
+    if (h->host) {
+        tgms::host::nearest_free(*field, values, r_free, max_shift, nearest, dsq);
+        return TGMS_OK;
+    }
+    // the map goes up, the middle pass runs in the handle's workspace, the outputs come down
+    const size_t N = (size_t)field->n[0] * field->n[1] * field->n[2];
+    Outputs out;
+    const auto oNear = out.add(nearest, N);
+    const auto oDsq = out.add(dsq, N);
+    float* dV;
+    int32_t* dWork;
+    const tgms_status s = stage(h, {input(&dV, values, N), output(&dWork, N), output(&out)});
+    if (s != TGMS_OK) return s;
+    TGMS_HIP(h, tgms::launch_nearest_free(*field, dV, r_free, max_shift, out.dev(oNear), out.dev(oDsq), dWork, h->stream));
+    return out.download(h);
+}
+
+tgms_status tgms_waypoints_repair_batch_dev(tgms_handle* h, int32_t B, const int32_t* d_so, const double* dW,
+                                            const double* dT, const tgms_field* field, const int32_t* d_nearest,
+                                            int32_t mode, double* dW_out, double* dT_out, int32_t* d_wp_flags,
+                                            int32_t* d_shift, int32_t* d_flags, void* stream) {
+    if (tgms_status e = enter(h, __func__); e != TGMS_OK) return e;
+    const tgms_status s = check_repair(h, B, field, d_nearest, mode, dT, dW_out, dT_out);
+    if (s != TGMS_OK) return s;
+    if (B == 0) return TGMS_OK;
+    if (!d_so || !dW) return set_err(h, TGMS_ERR_INVALID_ARG, "NULL device pointer");
+    TGMS_CHECK_ALIGNED(h, dW, dT, dW_out, dT_out);
+    TGMS_HIP(h, hipSetDevice(h->device));
+    TGMS_HIP(h, tgms::launch_repair(B, d_so, dW, dT, *field, d_nearest, mode, dW_out, dT_out, d_wp_flags, d_shift, d_flags,
+                                    static_cast<hipStream_t>(stream)));
+    return TGMS_OK;
+}
+
+tgms_status tgms_waypoints_repair_batch(tgms_handle* h, int32_t B, const int32_t* so, const double* waypoints,
+                                        const double* seg_times, const tgms_field* field, const float* values,
+                                        double r_free, int32_t max_shift, int32_t mode, double* waypoints_out,
+                                        double* seg_times_out, int32_t* wp_flags, int32_t* shift, int32_t* flags) {
+    if (tgms_status e = enter(h); e != TGMS_OK) return e;
+    tgms_status s = check_offsets(h, B, so, TGMS_MAX_SEGMENTS, nullptr, nullptr);
+    if (s != TGMS_OK) return s;
+    s = check_repair(h, B, field, values, mode, seg_times, waypoints_out, seg_times_out);
+    if (s != TGMS_OK) return s;
+    s = check_near(h, field, values, r_free, max_shift);
+    if (s != TGMS_OK) return s;
+    if (B == 0) return TGMS_OK;
+    if (!waypoints) return set_err(h, TGMS_ERR_INVALID_ARG, "NULL pointer");
+    if (h->host) {
+        tgms::host::waypoints_repair(B, so, waypoints, seg_times, *field, values, r_free, max_shift, mode, waypoints_out,
+                                     seg_times_out, wp_flags, shift, flags);
+        return TGMS_OK;
+    }
+    // the map goes up with the batch and its nearest-free map is built beside them, in the workspace
+    const size_t S = (size_t)so[B], n = (size_t)B;
+    const size_t N = (size_t)field->n[0] * field->n[1] * field->n[2];
+    Outputs out;
+    const auto oW = out.add(waypoints_out, (S + n) * 3), oT = out.add(seg_times_out, S);
+    const auto oWf = out.add(wp_flags, S + n), oSh = out.add(shift, S + n), oFl = out.add(flags, n);
+    double *dW, *dT;
+    float* dV;
+    int32_t *dSo, *dNear, *dWork;
+    s = stage(h, {input(&dW, waypoints, (S + n) * 3), input(&dT, seg_times, S), input(&dV, values, N),
+                  input(&dSo, so, n + 1), output(&dNear, N), output(&dWork, N), output(&out)});
+    if (s != TGMS_OK) return s;
+    TGMS_HIP(h, tgms::launch_nearest_free(*field, dV, r_free, max_shift, dNear, nullptr, dWork, h->stream));
+    TGMS_HIP(h, tgms::launch_repair(B, dSo, dW, dT, *field, dNear, mode, out.dev(oW), out.dev(oT), out.dev(oWf),
+                                    out.dev(oSh), out.dev(oFl), h->stream));
     return out.download(h);
 }
 

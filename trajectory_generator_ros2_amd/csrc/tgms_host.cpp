@@ -36,6 +36,7 @@
 #include "tgms_inflate_core.h"
 #include "tgms_neighbors_core.h"
 #include "tgms_separation_core.h"
+#include "tgms_repair_core.h"
 #include "tgms_reroute_core.h"
 #include "tgms_subdivide_core.h"
 #include "tgms_rate_core.h"
@@ -951,6 +952,75 @@ void reroute(int32_t B, const int32_t* so, const double* W, const double* T, con
     }
     so_out[B] = (int32_t)out;
     totals[0] = out;
+}
+
+void nearest_free(const tgms_field& fld, const float* values, double r_free, int32_t max_shift, int32_t* nearest,
+                  int32_t* dsq) {
+    namespace rp = tgms::repair;
+    const int64_t nx = fld.n[0], ny = fld.n[1], nz = fld.n[2], N = nx * ny * nz;
+    const int32_t K = rp::limit(max_shift);
+    const float rf = (float)r_free;
+    const size_t len = (size_t)std::max(ny, nz);
+    std::vector<int32_t> a((size_t)N), b((size_t)N), f(len), arg(len), val(len), s(len), t(len);
+    for (int64_t r = 0; r < ny * nz; ++r) rp::row_pass(values + r * nx, rf, (int32_t)nx, max_shift, a.data() + r * nx);
+    for (int64_t k = 0; k < nz; ++k)
+        for (int64_t i = 0; i < nx; ++i) {
+            const int32_t* const in = a.data() + k * nx * ny + i;
+            for (int64_t j = 0; j < ny; ++j) f[(size_t)j] = rp::f_row(in[j * nx], (int32_t)i, K);
+            rp::line_pass(f.data(), (int32_t)ny, K, arg.data(), val.data(), s.data(), t.data());
+            for (int64_t j = 0; j < ny; ++j) {
+                const int32_t w = arg[(size_t)j];
+                b[(size_t)(k * nx * ny + j * nx + i)] = w < 0 ? rp::NONE : rp::pack_yx(w, in[(int64_t)w * nx]);
+            }
+        }
+    for (int64_t j = 0; j < ny; ++j)
+        for (int64_t i = 0; i < nx; ++i) {
+            const int32_t* const in = b.data() + j * nx + i;
+            for (int64_t k = 0; k < nz; ++k) f[(size_t)k] = rp::f_plane(in[k * nx * ny], (int32_t)i, (int32_t)j, K);
+            rp::line_pass(f.data(), (int32_t)nz, K, arg.data(), val.data(), s.data(), t.data());
+            for (int64_t k = 0; k < nz; ++k) {
+                const int32_t w = arg[(size_t)k];
+                const int64_t node = k * nx * ny + j * nx + i;
+                const int32_t yx = w < 0 ? 0 : in[(int64_t)w * nx * ny];
+                nearest[node] = w < 0 ? rp::NONE : (int32_t)(((int64_t)w * ny + rp::site_y(yx)) * nx + rp::site_x(yx));
+                if (dsq) dsq[node] = w < 0 ? rp::NONE : val[(size_t)k];
+            }
+        }
+}
+
+void waypoints_repair(int32_t B, const int32_t* so, const double* W, const double* T, const tgms_field& fld,
+                      const float* values, double r_free, int32_t max_shift, int32_t mode, double* W_out, double* T_out,
+                      int32_t* wp_flags, int32_t* shift, int32_t* flags) {
+    namespace rp = tgms::repair;
+    const tgms::inflate::Grid g = tgms::inflate::make_grid(fld);
+    std::vector<int32_t> map((size_t)fld.n[0] * fld.n[1] * fld.n[2]);
+    nearest_free(fld, values, r_free, max_shift, map.data(), nullptr);
+    for (int32_t b = 0; b < B; ++b) {
+        const int64_t s0 = so[b];
+        const int M = so[b + 1] - so[b];
+        int32_t fl[TGMS_MAX_SEGMENTS + 1], all = 0;
+        for (int i = 0; i <= M; ++i) {
+            const int64_t row = s0 + i + b;
+            const double* w = W + row * 3;
+            const double p[3] = {w[0], w[1], w[2]};
+            const bool protect = (i == 0 && (mode & TGMS_RPR_KEEP_FIRST)) || (i == M && (mode & TGMS_RPR_KEEP_LAST));
+            double o[3];
+            int32_t sh;
+            fl[i] = rp::waypoint(g, map.data(), p, protect, o, sh);
+            std::copy(o, o + 3, W_out + row * 3);
+            if (wp_flags) wp_flags[row] = fl[i];
+            if (shift) shift[row] = sh;
+            all |= fl[i];
+        }
+        for (int i = 0; T_out && i < M; ++i) {
+            const double *w = W + (s0 + i + b) * 3, *o = W_out + (s0 + i + b) * 3;
+            const double w0[3] = {w[0], w[1], w[2]}, w1[3] = {w[3], w[4], w[5]};
+            const double p0[3] = {o[0], o[1], o[2]}, p1[3] = {o[3], o[4], o[5]};
+            const double t = T[s0 + i];
+            T_out[s0 + i] = ((fl[i] | fl[i + 1]) & TGMS_RPR_MOVED) ? rp::leg_time(t, w0, w1, p0, p1) : t;
+        }
+        if (flags) flags[b] = all;
+    }
 }
 
 void corridor(int32_t B, const int32_t* so, const double* T, const double* C, int64_t F, const double* faces,

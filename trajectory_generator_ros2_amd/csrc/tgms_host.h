@@ -116,6 +116,17 @@ void reroute(int32_t B, const int32_t* so, const double* W, const double* T, con
              const float* values, double r_free, int32_t margin, int32_t max_pieces, int32_t* so_out, double* W_out,
              double* T_out, int32_t* parent, int32_t* seg_flags, int32_t* hops, int64_t* totals, int32_t* flags);
 
+// The waypoint repair (include/tgms.h tgms_field_nearest_free, tgms_waypoints_repair_batch).
+// nearest_free: the row pass and the two lower-envelope passes of tgms_repair_core.h over the whole
+// grid; dsq is nullable.  waypoints_repair: that map first, then waypoint by waypoint the decision
+// of tgms_repair_core.h and leg by leg the time.  The offsets are valid; T and T_out are nullable
+// together, wp_flags, shift and flags nullable.
+void nearest_free(const tgms_field& field, const float* values, double r_free, int32_t max_shift, int32_t* nearest,
+                  int32_t* dsq);
+void waypoints_repair(int32_t B, const int32_t* so, const double* W, const double* T, const tgms_field& field,
+                      const float* values, double r_free, int32_t max_shift, int32_t mode, double* W_out, double* T_out,
+                      int32_t* wp_flags, int32_t* shift, int32_t* flags);
+
 // The corridor containment (include/tgms.h tgms_corridor_batch) of a whole batch, trajectory by
 // trajectory: per segment and face the item of tgms_corridor_core.h, the segment's fold in face
 // order, the trajectory's fold left to right.  face_offsets NULL: all F faces apply to every

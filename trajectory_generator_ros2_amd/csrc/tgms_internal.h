@@ -288,4 +288,18 @@ hipError_t launch_reroute(int32_t B, const int32_t* seg_offsets, const double* W
                           const int32_t* table, int32_t margin, int32_t max_pieces, void* scratch, int32_t* so_out,
                           double* W_out, double* T_out, int32_t* parent, int32_t* seg_flags, int32_t* hops,
                           int64_t* totals, int32_t* flags, hipStream_t stream);
+
+// Waypoint repair (tgms_repair.hip).  launch_nearest_free: per node of `values` on the grid `fld`
+// the linear index of the nearest free node within max_shift spacings (nearest [nz][ny][nx]) and
+// its squared lattice distance (dsq, nullable), TGMS_NEAR_NONE where there is none; three launches,
+// the middle pass in `work` (nearest_free_work_bytes, 4-byte aligned).  launch_repair: every
+// waypoint whose own seed holds a node that is not its own site moves onto the site of its nearest
+// node; the waypoints, the times (T and T_out nullable together), per waypoint its flag and shift,
+// per trajectory the OR of its flags (all three nullable); one launch.  Neither uses scratch.
+size_t nearest_free_work_bytes(const tgms_field& fld);
+hipError_t launch_nearest_free(const tgms_field& fld, const float* values, double r_free, int32_t max_shift,
+                               int32_t* nearest, int32_t* dsq, void* work, hipStream_t stream);
+hipError_t launch_repair(int32_t B, const int32_t* seg_offsets, const double* W, const double* T, const tgms_field& fld,
+                         const int32_t* nearest, int32_t mode, double* W_out, double* T_out, int32_t* wp_flags,
+                         int32_t* shift, int32_t* flags, hipStream_t stream);
 }  // namespace tgms

@@ -482,15 +482,66 @@ class Solver:
         fld = _lib.Field(origin, h, n)
         return int(self._L.tgms_field_edt_work_size(ctypes.byref(fld), _lib.EDT_SIGNED if signed else 0))
 
+    def field_nearest_free(self, values, origin, h: float, r_free: float, max_shift: int):
+        """Nearest-free map (include/tgms.h tgms_field_nearest_free): per node of the voxel field
+        `values` [nz,ny,nx] the linear index (k ny + j) nx + i of the nearest free node (value >=
+        float32(r_free)) within max_shift spacings, ties to the lowest index, and its squared lattice
+        distance; NEAR_NONE where there is none.  Returns (nearest, dsq), both [nz,ny,nx] int32."""
+        v = np.ascontiguousarray(values, dtype=np.float32)
+        assert v.ndim == 3, "values must be [nz, ny, nx]"
+        fld = _lib.Field(origin, h, v.shape[::-1])
+        nearest = np.full(v.shape, -2, dtype=np.int32)
+        dsq = np.full(v.shape, -2, dtype=np.int32)
+        self._check(self._L.tgms_field_nearest_free(
+            self._h, ctypes.byref(fld), _ptr(v), float(r_free), int(max_shift), _ptr(nearest), _ptr(dsq)))
+        return nearest, dsq
+
+    def field_nearest_free_work_size(self, origin, h: float, n) -> int:
+        """tgms_field_nearest_free_work_size: the bytes of field_nearest_free_device's workspace for a
+        grid of n = (nx, ny, nz) nodes; 0 for a grid the call refuses."""
+        fld = _lib.Field(origin, h, n)
+        return int(self._L.tgms_field_nearest_free_work_size(ctypes.byref(fld)))
+
+    def waypoints_repair(self, seg_offsets, waypoints, origin, h: float, values, r_free: float, max_shift: int,
+                         mode: int = 0, seg_times=None):
+        """Waypoint repair (include/tgms.h tgms_waypoints_repair_batch): every waypoint whose own cell
+        holds a non-free node of the voxel field `values` [nz,ny,nx] moves onto the free node nearest
+        to its nearest node, at most max_shift spacings away; mode: RPR_KEEP_FIRST | RPR_KEEP_LAST.
+        seg_offsets do not change.  Returns (waypoints' [S+B,3], seg_times' [S] (None without
+        seg_times), wp_flags [S+B] and flags [B] of RPR_* bits and FEAS_NONFINITE, shift [S+B]: the
+        squared lattice distance of a moved waypoint, NEAR_NONE otherwise)."""
+        so, W, T, _, _ = _csr(seg_offsets, waypoints, seg_times)
+        v = np.ascontiguousarray(values, dtype=np.float32)
+        assert v.ndim == 3, "values must be [nz, ny, nx]"
+        fld = _lib.Field(origin, h, v.shape[::-1])
+        B = so.shape[0] - 1
+        S = int(so[-1]) if B > 0 else 0
+        W2 = np.zeros((S + B, 3), dtype=np.float64)
+        T2 = None if T is None else np.zeros(S, dtype=np.float64)
+        wp_flags, shift = np.full(S + B, -2, dtype=np.int32), np.full(S + B, -2, dtype=np.int32)
+        flags = np.full(B, -2, dtype=np.int32)
+        self._check(self._L.tgms_waypoints_repair_batch(
+            self._h, B, _ptr(so), _ptr(W), _ptr(T), ctypes.byref(fld), _ptr(v), float(r_free), int(max_shift), int(mode),
+            _ptr(W2), _ptr(T2), _ptr(wp_flags), _ptr(shift), _ptr(flags)))
+        return W2, T2, wp_flags, flags, shift
+
     def corridor_from_map(self, seg_offsets, waypoints, seg_times, origin, h: float, values, r_free: float,
-                          max_grow: int, max_depth: int = _lib.SUB_MAX_DEPTH, reroute=None):
+                          max_grow: int, max_depth: int = _lib.SUB_MAX_DEPTH, reroute=None, repair=None):
         """From a voxel map to what corridor_loop() takes, on host arrays: corridor_subdivide, then
         corridor_inflate on its output.  Returns ((seg_offsets, waypoints, seg_times, faces,
         face_offsets), (sub_flags [B], sub_seg_flags [S'], inf_seg_flags [S'], inf_flags [B])); a
         segment with SUB_BLOCKED is the one with INF_BLOCKED and needs re-routing.  reroute = (margin,
         max_pieces): corridor_reroute runs between the two; the batch and the inflation flags are those
         of its output (the subdivision's segment flags stay those of the subdivision's S' rows) and the
-        second tuple gains (rrt_flags [B], rrt_seg_flags [S''], rrt_parent [S''], rrt_hops [S'])."""
+        second tuple gains (rrt_flags [B], rrt_seg_flags [S''], rrt_parent [S''], rrt_hops [S']).
+        repair = (max_shift, mode): waypoints_repair runs first, the rest sees its waypoints and times,
+        and the second tuple gains, last, (rpr_flags [B], rpr_wp_flags [S+B], rpr_shift [S+B])."""
+        rpr = ()
+        if repair is not None:
+            max_shift, mode = repair
+            waypoints, seg_times, rpr_wp, rpr_fl, rpr_shift = self.waypoints_repair(
+                seg_offsets, waypoints, origin, h, values, r_free, max_shift, mode, seg_times)
+            rpr = (rpr_fl, rpr_wp, rpr_shift)
         so, W, T, _, sub_seg, sub_fl = self.corridor_subdivide(seg_offsets, waypoints, origin, h, values, r_free,
                                                                max_depth, seg_times)
         rrt = ()
@@ -500,7 +551,7 @@ class Solver:
                                                                                  margin, max_pieces, T)
             rrt = (rrt_fl, rrt_seg, rrt_par, rrt_hops)
         _, faces, fo, inf_seg, inf_fl = self.corridor_inflate(so, W, origin, h, values, r_free, max_grow)
-        return (so, W, T, faces, fo), (sub_fl, sub_seg, inf_seg, inf_fl) + rrt
+        return (so, W, T, faces, fo), (sub_fl, sub_seg, inf_seg, inf_fl) + rrt + rpr
 
     def refine(self, seg_offsets, waypoints, seg_times, end_derivs=None, k_T: float = 1.0, eta: float = 0.1,
                iters: int = 10, coeffs: bool = True):
@@ -777,6 +828,28 @@ class Solver:
             _ptr(d_table), int(margin), int(max_pieces), _ptr(d_seg_offsets_out), _ptr(d_waypoints_out),
             _ptr(d_seg_times_out), _ptr(d_parent), _ptr(d_seg_flags_out), _ptr(d_hops), _ptr(d_totals), _ptr(d_flags),
             ctypes.c_void_p(stream)))
+
+    def field_nearest_free_device(self, origin, h: float, n, d_values, r_free: float, max_shift: int, d_nearest, d_work,
+                                  d_dsq=None, stream: int = 0) -> None:
+        """tgms_field_nearest_free_dev: n = (nx, ny, nz), d_values fp32 with x fastest; d_nearest and
+        d_dsq (optional) int32 of the same shape; d_work of field_nearest_free_work_size bytes.  Three
+        launches, no handle scratch: capturable."""
+        fld = _lib.Field(origin, h, n)
+        self._check(self._L.tgms_field_nearest_free_dev(
+            self._h, ctypes.byref(fld), _ptr(d_values), float(r_free), int(max_shift), _ptr(d_nearest), _ptr(d_dsq),
+            _ptr(d_work), ctypes.c_void_p(stream)))
+
+    def waypoints_repair_device(self, B: int, d_seg_offsets, d_waypoints, origin, h: float, n, d_nearest, mode: int,
+                                d_waypoints_out, d_seg_times=None, d_seg_times_out=None, d_wp_flags=None, d_shift=None,
+                                d_flags=None, stream: int = 0) -> None:
+        """tgms_waypoints_repair_batch_dev: d_nearest of field_nearest_free_device for the same grid;
+        d_waypoints_out [S+B,3], d_seg_times_out [S] (with d_seg_times, or neither), d_wp_flags and
+        d_shift [S+B] int32, d_flags [B] int32.  One launch, no handle scratch: capturable."""
+        fld = _lib.Field(origin, h, n)
+        self._check(self._L.tgms_waypoints_repair_batch_dev(
+            self._h, int(B), _ptr(d_seg_offsets), _ptr(d_waypoints), _ptr(d_seg_times), ctypes.byref(fld),
+            _ptr(d_nearest), int(mode), _ptr(d_waypoints_out), _ptr(d_seg_times_out), _ptr(d_wp_flags), _ptr(d_shift),
+            _ptr(d_flags), ctypes.c_void_p(stream)))
 
 
 def sample_count(total_T: float, dt: float) -> int:
