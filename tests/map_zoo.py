@@ -9,8 +9,9 @@ against each other, or the same scene is placed elsewhere in a larger grid:
     C  the EDT against itself: axis orders and reflections, embedding, one more node, the two modes
     D  the summed-volume table: closed forms, chunk and unroll seams, axis orders
     E  inflation and subdivision: a cavity with a known box and round count, placement, reversal
+    F  subdivision and re-route: a full tile of 64 output rows, a bad segment count inside a tile
 Backend-agnostic like the three reference files: a backend is anything with field_edt(...),
-corridor_inflate(...) and corridor_subdivide(...) (a Solver has them; the GPU file wraps the device
+corridor_inflate(...), corridor_subdivide(...) and for F corridor_reroute(...) (a Solver has them; the GPU file wraps the device
 entry points the same way).  The table checks take the function occupancy(origin, h, values,
 r_free) -> table.
 
@@ -23,8 +24,10 @@ import numpy as np
 
 import edt_ref as ER
 import inflate_ref as IR
+import reroute_ref as RR
 import subdivide_ref as SR
-from trajectory_generator_ros2_amd import EDT_NONE, INF_BLOCKED, INF_CAPPED, SUB_BLOCKED, SUB_DONE
+from trajectory_generator_ros2_amd import (EDT_NONE, FEAS_NONFINITE, INF_BLOCKED, INF_CAPPED, NEAR_NONE, SUB_BLOCKED,
+                                           SUB_DONE)
 
 Map = namedtuple("Map", "occ Do Df")  # uint8 [nz, ny, nx]; int64 squares, EDT_NONE where the set is empty
 
@@ -542,3 +545,83 @@ def check_subdivide_reversal(be):
     back = be.corridor_subdivide(so, Wr, P_ORIGIN, P_H, v, 0.3, 4, Tr)
     SR.assert_same(mirrored(so, back), base, "reversal")
     assert not SR.same_bits(back[1], base[1])
+
+
+# ---- F. the tiles of a rebuilt batch: the row map of the subdivision's and the re-route's write ----
+
+FULL_TILE = (16, 16, 16, 16, 1)  # 64 rows in one tile of four trajectories, then a tile of one lane
+BAD_BETWEEN = (1, 0, 16)         # a count outside 1..16 between two good trajectories of one tile
+
+
+def counted_batch(counts, lo, hi, reach, h, seed=3):
+    """Trajectories with the given segment counts: every waypoint within `reach` nodes of its
+    trajectory's first per axis and inside lo..hi, in node units of spacing h."""
+    rng = np.random.default_rng(seed)
+    so = np.concatenate([[0], np.cumsum(counts)]).astype(np.int32)
+    B, S = len(counts), int(so[-1])
+    first = np.repeat(rng.uniform(lo, hi, size=(B, 3)), np.asarray(counts) + 1, axis=0)
+    W = np.clip(first + rng.uniform(-reach, reach, size=(S + B, 3)), lo, hi) * h
+    return so, W, rng.uniform(0.5, 4.0, size=S)
+
+
+def sub_scene(counts):
+    """The subdivision's arguments behind (so, W, T): the 17^3 grid with 60 non-free nodes, depth 4."""
+    v = SR.g_values(SR.random_nodes(60), bad=0.25)
+    return counted_batch(counts, 0.25, 15.75, 16.0, SR.G_H), (SR.G_ORIGIN, SR.G_H, v, 0.3, 4)
+
+
+def rrt_scene(counts):
+    """The re-route's: the maze of reroute_ref.py, legs of at most three nodes, margin 3, 8 pieces."""
+    return counted_batch(counts, 0.25, 22.75, 3.0, RR.H), (RR.O, RR.H, RR.maze()[3], RR.RF, 3, 8)
+
+
+def check_full_tile(be):
+    """Every trajectory of the first tile already has 16 segments, so no leg may gain a row: the
+    write maps 64 output rows, one per lane, and the fifth trajectory is a tile of one lane."""
+    (so, W, T), a = sub_scene(FULL_TILE)
+    got = be.corridor_subdivide(so, W, *a, T)
+    SR.assert_same(got, SR.reference(so, W, T, *a), "subdivide")
+    assert list(np.diff(got[0][:5])) == [16] * 4 and (got[4][:64] & SUB_BLOCKED).any()
+    (so, W, T), a = rrt_scene(FULL_TILE)
+    got = be.corridor_reroute(so, W, *a, T)
+    RR.assert_same(got, RR.reference(so, W, T, *a), "re-route")
+    assert list(np.diff(got[0][:5])) == [16] * 4 and (got[6][:4] != 0).any()
+
+
+def with_placeholder(want, so, at, count, hops=False):
+    """The outputs `want` of a batch after a trajectory of `count` segments (0 or 17: a bad count)
+    is inserted at position `at`: one placeholder row there, every other row as it was.  The hops
+    are per input segment and those of the inserted rows are not written: None here."""
+    s2, w2 = int(want[0][at]), int(want[0][at]) + at
+    parent = want[3].copy()
+    parent[s2:] += count  # the input rows behind the inserted trajectory moved
+    i32 = lambda *p: np.concatenate(p).astype(np.int32)  # noqa: E731
+    out = [i32(want[0][:at + 1], want[0][at:] + 1), np.concatenate([want[1][:w2], np.full((2, 3), np.nan), want[1][w2:]]),
+           np.concatenate([want[2][:s2], [np.nan], want[2][s2:]]), i32(parent[:s2], [NEAR_NONE], parent[s2:]),
+           i32(want[4][:s2], [FEAS_NONFINITE], want[4][s2:])]
+    return tuple(out + ([None] if hops else []) + [i32(want[-1][:at], [FEAS_NONFINITE], want[-1][at:])])
+
+
+def check_bad_between(run, scene, reference, hops=False):
+    """run(so, W, T, *scene arguments) is the device entry point on offsets no host-pointer call
+    accepts.  The good trajectories of BAD_BETWEEN against the reference of the batch without the
+    bad one; the first has one leg, the last sixteen, so the placeholder is row `rows of the first`
+    of its tile and its own trajectory's lanes are none."""
+    at = BAD_BETWEEN.index(0)
+    (so, W, T), a = scene([c for c in BAD_BETWEEN if c])
+    want = reference(so, W, T, *a)
+    w = int(so[at]) + at
+    so_bad = np.concatenate([so[:at + 1], so[at:]]).astype(np.int32)
+    W_bad = np.concatenate([W[:w], np.full((1, 3), 3.5), W[w:]])
+    got = run(so_bad, W_bad, T, *a)
+    for k, (g, e) in enumerate(zip(got, with_placeholder(want, so, at, 0, hops))):
+        if e is None:
+            continue
+        assert g.shape == e.shape, k
+        if e.dtype.kind == "f":  # the placeholder's NaN by place, every other double to the bit
+            assert np.array_equal(np.isnan(g), np.isnan(e)), k
+            g, e = g[~np.isnan(e)], e[~np.isnan(e)]
+        assert SR.same_bits(g, e), k
+    if hops:
+        assert np.array_equal(got[5], want[5])  # no input segment was inserted
+    return got

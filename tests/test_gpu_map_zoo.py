@@ -18,6 +18,7 @@ import edt_ref as ER
 import inflate_ref as IR
 import map_zoo as MZ
 from test_gpu_inflate import Device as InflateDevice
+from test_gpu_reroute import run_device as run_reroute
 from test_gpu_subdivide import run_device
 
 pytestmark = pytest.mark.gpu
@@ -188,3 +189,20 @@ def test_subdivision_ignores_the_placement(be, host):
 
 def test_subdivision_of_the_reversed_flight_is_the_mirror_image(be):
     MZ.check_subdivide_reversal(be)
+
+
+# ---- F. the row map of the two writes ----
+
+class Rebuilds(Device):
+    def corridor_reroute(self, so, W, origin, h, values, r_free, margin, max_pieces, seg_times=None):
+        return run_reroute(self.s, so, W, seg_times, origin, h, values, r_free, margin, max_pieces)
+
+
+def test_full_tile_then_a_tile_of_one_lane(solver):
+    MZ.check_full_tile(solver)
+    MZ.check_full_tile(Rebuilds(solver))
+
+
+def test_bad_count_between_two_good_trajectories(solver):
+    MZ.check_bad_between(lambda so, W, T, *a: run_device(solver, so, W, T, *a), MZ.sub_scene, MZ.SR.reference)
+    MZ.check_bad_between(lambda so, W, T, *a: run_reroute(solver, so, W, T, *a), MZ.rrt_scene, MZ.RR.reference, hops=True)

@@ -135,3 +135,17 @@ def test_subdivision_ignores_the_placement(host):
 def test_subdivision_of_the_reversed_flight_is_the_mirror_image(host):
     MZ.check_subdivide_reversal(MZ.Reference())
     MZ.check_subdivide_reversal(host)
+
+
+def test_full_tile_then_a_tile_of_one_lane(host):
+    MZ.check_full_tile(host)
+
+
+def test_placeholder_splice_on_the_reference():
+    """with_placeholder against nothing but itself: a 17-segment trajectory spliced into the
+    outputs of BAD_BETWEEN's good trajectories keeps their rows and adds one of each kind."""
+    (so, W, T), a = MZ.sub_scene([c for c in MZ.BAD_BETWEEN if c])
+    want = MZ.SR.reference(so, W, T, *a)
+    exp = MZ.with_placeholder(want, so, 1, 17)
+    assert [len(e) - len(w) for e, w in zip(exp, want)] == [1, 2, 1, 1, 1, 1] and exp[0][-1] == want[0][-1] + 1
+    assert np.isnan(exp[2][want[0][1]]) and exp[3][want[0][1] + 1] == want[3][want[0][1]] + 17

@@ -34,17 +34,8 @@
 namespace tgms {
 namespace {
 
-using namespace seg_tile;  // TILE, SEGS, Tile, load_tile, lane_segment, lane_knot
+using namespace seg_tile;  // the tile by grid-stride, one wavefront a workgroup: not wave_tile
 constexpr int SCAN = 256;  // entries of one workgroup of the scan (tests/test_gpu_split.py pins its seams)
-
-__device__ __forceinline__ int wave_inclusive(int v, int lane) {
-#pragma unroll
-    for (int o = 1; o < W64; o <<= 1) {
-        const int up = __shfl_up(v, o, W64);
-        v += lane >= o ? up : 0;
-    }
-    return v;
-}
 
 // The face span of segment gs: its first face and count; -1: not usable.
 __device__ __forceinline__ void face_span(int64_t F, const int64_t* __restrict__ fo, int64_t gs, int64_t& fb,
@@ -234,20 +225,11 @@ __global__ __launch_bounds__(SCAN) void k_scan_add(int32_t B, const int32_t* __r
 }
 
 __global__ void k_split_empty(int64_t F1, int32_t* __restrict__ so_out, int64_t* __restrict__ totals) {
-    if (threadIdx.x == 0 && blockIdx.x == 0) {
-        so_out[0] = 0;
-        totals[0] = 0;
-        totals[1] = F1;
-    }
+    empty_batch(so_out, totals);
+    if (threadIdx.x == 0 && blockIdx.x == 0) totals[1] = F1;
 }
 
 // ---- the write ----
-
-__device__ __forceinline__ void copy3(double* __restrict__ dst, const double* __restrict__ src) {
-    dst[0] = src[0];
-    dst[1] = src[1];
-    dst[2] = src[2];
-}
 
 __global__ __launch_bounds__(W64) void k_split_write(
     int32_t B, const int32_t* __restrict__ so, const double* __restrict__ W, const double* __restrict__ T,
@@ -398,35 +380,17 @@ __global__ __launch_bounds__(W64) void k_split_write(
     }
 }
 
-struct Scratch {
-    int64_t *cntF, *sumS, *sumF;
+struct Scratch : ScanScratch {
     int32_t *cntS, *mask;
-    size_t bytes;
+    Scratch(int32_t B, void* base) : ScanScratch(B, base, false) {  // the scan's totals are the caller's
+        cntS = take<int32_t>(n);
+        mask = take<int32_t>(n);
+    }
 };
-
-Scratch layout(int32_t B, void* base) {
-    const size_t n = (size_t)std::max(B, 0), nblk = (n + SCAN - 1) / SCAN;
-    auto up = [](size_t v) { return (v + 255) & ~size_t(255); };
-    char* p = static_cast<char*>(base);
-    size_t off = 0;
-    Scratch s;
-    s.cntF = reinterpret_cast<int64_t*>(p + off);
-    off = up(off + n * sizeof(int64_t));
-    s.sumS = reinterpret_cast<int64_t*>(p + off);
-    off = up(off + nblk * sizeof(int64_t));
-    s.sumF = reinterpret_cast<int64_t*>(p + off);
-    off = up(off + nblk * sizeof(int64_t));
-    s.cntS = reinterpret_cast<int32_t*>(p + off);
-    off = up(off + n * sizeof(int32_t));
-    s.mask = reinterpret_cast<int32_t*>(p + off);
-    off = up(off + n * sizeof(int32_t));
-    s.bytes = off;
-    return s;
-}
 
 }  // namespace
 
-size_t corridor_split_scratch_bytes(int32_t B) { return layout(B, nullptr).bytes; }
+size_t corridor_split_scratch_bytes(int32_t B) { return Scratch(B, nullptr).off; }
 
 size_t count_scan_blocks(int32_t B) { return ((size_t)std::max(B, 0) + SCAN - 1) / SCAN; }
 
@@ -450,7 +414,7 @@ hipError_t launch_corridor_split(int32_t B, const int32_t* seg_offsets, const do
         TGMS_LAUNCH(k_split_empty, dim3(1), dim3(W64), 0, stream, face_offsets ? (int64_t)0 : F, so_out, totals);
         return hipSuccess;
     }
-    const Scratch s = layout(B, scratch);
+    const Scratch s(B, scratch);
     const int64_t tiles = ((int64_t)B + TILE - 1) / TILE;
     const unsigned blocks = (unsigned)std::min<int64_t>(tiles, 4096);
     TGMS_LAUNCH(k_split_plan, dim3(blocks), dim3(W64), 0, stream, B, seg_offsets, W, T, C, F, face_offsets, seg_rec,

@@ -2,17 +2,14 @@
 //
 // Every trajectory of a solved batch is restarted from its state at t_cut: the segments behind
 // the cut go, the one it falls in is shortened, and the batch (offsets, waypoints, times, end
-// derivatives, coefficients) is rebuilt on the device.  tgms_cut_core.h has every decision; this
-// file has the mapping, which is the corridor split's.  Three stages, launched in order on one
-// stream:
-//   1. k_cut_plan: the segment tile (a wavefront per TILE = 4 trajectories, a lane per segment,
-//      grid-stride).  The lanes of a trajectory form its knots with shuffles, count the interior
+// derivatives, coefficients) is rebuilt on the device.  tgms_cut_core.h has every decision.  Three
+// stages, launched in order on one stream:
+//   1. k_cut_plan: the segment tile of tgms_seg_tile.h, tiles by grid-stride, one wavefront a
+//      workgroup.  The lanes of a trajectory form its knots with shuffles, count the interior
 //      knots at or before the cut with a ballot, fetch the knot and time of that segment with
 //      two more shuffles and resolve the plan: the first kept segment s, the local time, the
 //      flags, the new segment count and t0.
-//   2. the scan: the exclusive prefix sum of the new segment counts over B, the split's three
-//      k_scan_* launches from where they are (launch_count_scan; its second, int64 lane of counts
-//      is zero here).
+//   2. the scan of the new segment counts (launch_count_scan).
 //   3. k_cut_write: the tile again.  The lane of a kept segment writes its time, its start
 //      waypoint and its parent row; the lane of the first one also the end derivatives and,
 //      where the cut is inside the segment, the Taylor-shifted row, computed in registers with
@@ -32,7 +29,7 @@
 namespace tgms {
 namespace {
 
-using namespace seg_tile;  // TILE, SEGS, Tile, load_tile, lane_segment, lane_knot
+using namespace seg_tile;
 
 constexpr int ROW_ITEMS = 12;  // a coefficient row [3][8] as 16-byte items
 constexpr int64_t SRC_SELF = -1, SRC_NAN = -2;  // an output row its own lane writes; a placeholder's
@@ -106,30 +103,16 @@ __global__ __launch_bounds__(W64) void k_cut_plan(int32_t B, const int32_t* __re
         }
 #pragma unroll
         for (int t = 0; t < TILE; ++t) {
-            if (!(x.oob[t] && lane == t)) continue;  // a bad count: one placeholder segment
-            const int64_t b = b0 + t;
-            cntS[b] = 1;
-            cntF[b] = 0;
-            code[b] = pack(cut::PLACEHOLDER, 0);
-            tloc[b] = 0.0;
-            if (t0_out) t0_out[b] = __builtin_nan("");
-            if (flags) flags[b] = TGMS_FEAS_NONFINITE;
+            if (!(x.oob[t] && lane == t)) continue;  // a bad count: the placeholder and the cut's own words of it
+            plan_placeholder(b0 + t, cntS, cntF, flags);
+            code[b0 + t] = pack(cut::PLACEHOLDER, 0);
+            tloc[b0 + t] = 0.0;
+            if (t0_out) t0_out[b0 + t] = __builtin_nan("");
         }
     }
 }
 
-__global__ void k_cut_empty(int32_t* __restrict__ so_out, int64_t* __restrict__ totals) {
-    if (threadIdx.x == 0 && blockIdx.x == 0) {
-        so_out[0] = 0;
-        totals[0] = 0;
-    }
-}
-
-__device__ __forceinline__ void copy3(double* __restrict__ dst, const double* __restrict__ src) {
-    dst[0] = src[0];
-    dst[1] = src[1];
-    dst[2] = src[2];
-}
+__global__ void k_cut_empty(int32_t* __restrict__ so_out, int64_t* __restrict__ totals) { empty_batch(so_out, totals); }
 
 __global__ __launch_bounds__(W64) void k_cut_write(
     int32_t B, const int32_t* __restrict__ so, const double* __restrict__ W, const double* __restrict__ T,
@@ -282,40 +265,19 @@ __global__ __launch_bounds__(W64) void k_cut_write(
     }
 }
 
-struct Scratch {
-    int64_t *cntF, *sumS, *sumF, *totals;
+struct Scratch : ScanScratch {
     double* tloc;
     int32_t *cntS, *code;
-    size_t bytes;
+    Scratch(int32_t B, void* base) : ScanScratch(B, base, true) {
+        tloc = take<double>(n);
+        cntS = take<int32_t>(n);
+        code = take<int32_t>(n);
+    }
 };
-
-Scratch layout(int32_t B, void* base) {
-    const size_t n = (size_t)std::max(B, 0), nblk = count_scan_blocks(B);
-    auto up = [](size_t v) { return (v + 255) & ~size_t(255); };
-    char* p = static_cast<char*>(base);
-    size_t off = 0;
-    Scratch s;
-    s.cntF = reinterpret_cast<int64_t*>(p + off);
-    off = up(off + n * sizeof(int64_t));
-    s.sumS = reinterpret_cast<int64_t*>(p + off);
-    off = up(off + nblk * sizeof(int64_t));
-    s.sumF = reinterpret_cast<int64_t*>(p + off);
-    off = up(off + nblk * sizeof(int64_t));
-    s.totals = reinterpret_cast<int64_t*>(p + off);
-    off = up(off + 2 * sizeof(int64_t));
-    s.tloc = reinterpret_cast<double*>(p + off);
-    off = up(off + n * sizeof(double));
-    s.cntS = reinterpret_cast<int32_t*>(p + off);
-    off = up(off + n * sizeof(int32_t));
-    s.code = reinterpret_cast<int32_t*>(p + off);
-    off = up(off + n * sizeof(int32_t));
-    s.bytes = off;
-    return s;
-}
 
 }  // namespace
 
-size_t cut_scratch_bytes(int32_t B) { return layout(B, nullptr).bytes; }
+size_t cut_scratch_bytes(int32_t B) { return Scratch(B, nullptr).off; }
 
 hipError_t launch_cut(int32_t B, const int32_t* seg_offsets, const double* W, const double* T, const double* ED,
                       const double* C, const double* t_cut, double min_frac, void* scratch, int32_t* so_out,
@@ -325,7 +287,7 @@ hipError_t launch_cut(int32_t B, const int32_t* seg_offsets, const double* W, co
         TGMS_LAUNCH(k_cut_empty, dim3(1), dim3(W64), 0, stream, so_out, totals);
         return hipSuccess;
     }
-    const Scratch s = layout(B, scratch);
+    const Scratch s(B, scratch);
     const int64_t tiles = ((int64_t)B + TILE - 1) / TILE;
     const unsigned blocks = (unsigned)std::min<int64_t>(tiles, 4096);
     TGMS_LAUNCH(k_cut_plan, dim3(blocks), dim3(W64), 0, stream, B, seg_offsets, W, T, ED, C, t_cut, min_frac, s.cntS,

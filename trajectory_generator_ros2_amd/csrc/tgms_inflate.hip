@@ -14,14 +14,12 @@
 //     before it adds and stores them, so the loads of a step are in flight together and every
 //     wave-instruction moves 256 contiguous bytes.  Integer sums: no order can change a bit.
 //
-// k_inflate: the segment tile of tgms_seg_tile.h, a wavefront per four trajectories and a lane
-// per segment, so a lane knows its trajectory and with it its waypoint rows s + b and s + b + 1;
-// four wavefronts per workgroup, each with a tile of its own, no LDS and no barrier.  A lane
-// runs its segment's growth alone: every slab test is eight 4-byte gathers from the table
-// issued together and one count, at most 6 max_grow of them one after the other.  What the
-// kernel waits for is those gathers; only other wavefronts hide them, so the registers are kept
-// to full occupancy (DESIGN.md has the counts).  The trajectory's flags are the OR of its
-// lanes' by four ballots.
+// k_inflate: a lane per segment (wave_tile of tgms_seg_tile.h), so a lane knows its trajectory
+// and with it its waypoint rows s + b and s + b + 1.  A lane runs its segment's growth alone:
+// every slab test is eight 4-byte gathers from the table issued together and one count, at most
+// 6 max_grow of them one after the other.  What the kernel waits for is those gathers; only
+// other wavefronts hide them, so the registers are kept to full occupancy (DESIGN.md has the
+// counts).
 #include <algorithm>
 
 #include "tgms_device.h"
@@ -32,10 +30,8 @@
 namespace tgms {
 namespace {
 
-using namespace seg_tile;  // TILE, Tile, load_tile, lane_segment
+using namespace seg_tile;  // BLOCK and WAVES are k_occ_rows' too
 
-constexpr int BLOCK = 256;                // threads of every workgroup here
-constexpr int WAVES = BLOCK / W64;        // its wavefronts
 constexpr int LINE_UNROLL = 8;            // entries of a line a lane has in flight
 constexpr int32_t MAX_BLOCKS = 256 * 8;   // grid-stride beyond: eight workgroups a CU
 
@@ -95,20 +91,12 @@ __global__ __launch_bounds__(BLOCK) void k_inflate(int32_t B, const int32_t* __r
                                                    int32_t* __restrict__ box, double* __restrict__ faces,
                                                    int64_t* __restrict__ face_offsets, int32_t* __restrict__ seg_flags,
                                                    int32_t* __restrict__ flags) {
-    const int lane = threadIdx.x & (W64 - 1);
-    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x / W64));
-    const int64_t b0 = ((int64_t)blockIdx.x * WAVES + wave) * TILE;
-    if (b0 >= B) return;  // the whole wavefront
-    const int nb = (int)std::min<int64_t>(TILE, B - b0);
-    Tile x;
-    load_tile(seg_offsets, b0, nb, x);
-    int tr, sb, M;
-    int64_t gs;
-    lane_segment(x, lane, tr, sb, M, gs);
-    const bool mine = lane < x.base[TILE];
+    Lane l;
+    if (!wave_tile(B, seg_offsets, l)) return;
+    const int64_t gs = l.gs;
     int32_t fl = 0;
-    if (mine) {
-        const double* w = W + (gs + b0 + tr) * 3;  // rows s + b and s + b + 1
+    if (l.mine) {
+        const double* w = W + (gs + l.b0 + l.tr) * 3;  // rows s + b and s + b + 1
         const double w0[3] = {w[0], w[1], w[2]}, w1[3] = {w[3], w[4], w[5]};
         int32_t bx[6];
         double fc[6];
@@ -129,22 +117,12 @@ __global__ __launch_bounds__(BLOCK) void k_inflate(int32_t B, const int32_t* __r
         }
         if (face_offsets) {
             face_offsets[gs] = 6 * gs;
-            if (b0 + tr == B - 1 && lane - sb == M - 1) face_offsets[gs + 1] = 6 * (gs + 1);
+            if (l.b0 + l.tr == B - 1 && l.lane - l.sb == l.M - 1) face_offsets[gs + 1] = 6 * (gs + 1);
         }
         if (seg_flags) seg_flags[gs] = fl;
     }
-    // the trajectory's flags: the OR over its lanes sb .. sb + M - 1, bit by bit
-    const unsigned long long span = mine ? ((1ull << M) - 1ull) << sb : 0ull;  // M <= 16
     constexpr int32_t BITS[4] = {TGMS_INF_BLOCKED, TGMS_INF_OUTSIDE, TGMS_INF_CAPPED, TGMS_FEAS_NONFINITE};
-    int32_t all = 0;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) all |= (__ballot((fl & BITS[i]) != 0) & span) != 0ull ? BITS[i] : 0;
-    if (flags) {
-        if (mine && lane == sb) flags[b0 + tr] = all;
-#pragma unroll
-        for (int t = 0; t < TILE; ++t)
-            if (x.oob[t] && lane == t) flags[b0 + t] = TGMS_FEAS_NONFINITE;  // a bad count: nothing read
-    }
+    store_flags(l, trajectory_flags(fl, l.mine, l.sb, l.M, BITS), flags);
 }
 
 }  // namespace
@@ -168,8 +146,7 @@ hipError_t launch_inflate(int32_t B, const int32_t* seg_offsets, const double* W
                           const int32_t* table, int32_t max_grow, int32_t* box, double* faces, int64_t* face_offsets,
                           int32_t* seg_flags, int32_t* flags, hipStream_t stream) {
     if (B <= 0) return hipSuccess;
-    const int64_t tiles = ((int64_t)B + TILE - 1) / TILE;
-    TGMS_LAUNCH(k_inflate, dim3((unsigned)((tiles + WAVES - 1) / WAVES)), dim3(BLOCK), 0, stream, B, seg_offsets, W,
+    TGMS_LAUNCH(k_inflate, dim3(wave_tile_blocks(B)), dim3(BLOCK), 0, stream, B, seg_offsets, W,
                 inflate::make_grid(fld), table, max_grow, box, faces, face_offsets, seg_flags, flags);
     return hipSuccess;
 }

@@ -185,13 +185,35 @@ hipError_t launch_corridor_split(int32_t B, const int32_t* seg_offsets, const do
                                  int64_t* fo_out, int32_t* parent, int64_t* totals, int32_t* flags,
                                  hipStream_t stream);
 
-// The split's prefix sums for the other compactions (tgms_cut.hip), launched from where they are:
-// so_out [B+1] = the exclusive int32 scan of cntS [B] with the total at [B], cntF [B] (int64)
-// scanned in place, totals [2] = both sums (totals[1] = shared_F when that is >= 0).  sumS and
-// sumF hold count_scan_blocks(B) entries each.  Three launches; B > 0.
+// The prefix sums of every call that rebuilds a batch (split, cut, subdivision, re-route), the
+// k_scan_* kernels of tgms_corridor_split.hip: so_out [B+1] = the exclusive int32 scan of cntS
+// [B] with the total at [B], cntF [B] (int64) scanned in place, totals [2] = both sums (totals[1]
+// = shared_F when that is >= 0).  sumS and sumF hold count_scan_blocks(B) entries each.  Three
+// launches; B > 0.
 size_t count_scan_blocks(int32_t B);
 hipError_t launch_count_scan(int32_t B, const int32_t* cntS, int64_t* cntF, int64_t* sumS, int64_t* sumF,
                              int64_t shared_F, int32_t* so_out, int64_t* totals, hipStream_t stream);
+
+// The scratch of such a call, carved in 256-byte steps: the scan's cntF, sumS, sumF and (not in
+// the split, which scans into the caller's) totals [2] first; take<T>(count) hands out each
+// call's own fields after them, cntS among them, and `off` is then the size.  n = max(B, 0).
+struct ScanScratch {
+    char* p;
+    size_t n, off = 0;
+    int64_t *cntF, *sumS, *sumF, *totals = nullptr;
+    template <class T>
+    T* take(size_t count) {
+        T* const at = reinterpret_cast<T*>(p + off);
+        off = (off + count * sizeof(T) + 255) & ~size_t(255);
+        return at;
+    }
+    ScanScratch(int32_t B, void* base, bool with_totals) : p(static_cast<char*>(base)), n(B > 0 ? (size_t)B : 0) {
+        cntF = take<int64_t>(n);
+        sumS = take<int64_t>(count_scan_blocks(B));
+        sumF = take<int64_t>(count_scan_blocks(B));
+        if (with_totals) totals = take<int64_t>(2);
+    }
+};
 
 // Replan cut (tgms_cut.hip): every trajectory restarted from its state at t_cut [B]; the new
 // offsets, waypoints, times, end derivatives, coefficients (nullable), parent rows (nullable), t0

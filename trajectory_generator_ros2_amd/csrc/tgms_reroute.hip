@@ -3,12 +3,12 @@
 // The step between the subdivision and the inflation: a leg whose own lattice box holds a non-free
 // node gets a detour through the free nodes of a bounded window of the map, reduced to a few
 // pieces with free boxes, and the batch (offsets, waypoints, times, parents) is rebuilt on the
-// device.  tgms_reroute_core.h has every decision; this file has the mapping.  Stages, launched
-// in order on one stream:
-//   1. k_rrt_classify: the segment tile of tgms_seg_tile.h, a wavefront per TILE = 4 trajectories
-//      and a lane per leg.  A leg that is not searched leaves its record; a candidate appends its
-//      slot to the candidate list (one atomic per wavefront; the order of the list is not part of
-//      any result).  The list and its count stay on the device: no host sync.
+// device.  tgms_reroute_core.h has every decision, tgms_seg_tile.h the mapping of every stage but
+// the search.  Stages, launched in order on one stream:
+//   1. k_rrt_classify: a lane per leg (wave_tile).  A leg that is not searched leaves its record;
+//      a candidate appends its slot to the candidate list (one atomic per wavefront; the order of
+//      the list is not part of any result).  The list and its count stay on the device: no host
+//      sync.
 //   2. k_rrt_search, the hot path: a persistent grid of SEARCH_BLOCKS workgroups strides over the
 //      candidate list; no workgroup waits for another.  A workgroup holds the window's distances
 //      as uint16 dist[Nw] in dynamic LDS (64 KiB at the cap of 32,768 nodes, and three control
@@ -23,11 +23,11 @@
 //      one step at a time (six lanes look at the six neighbours, a ballot picks the first), the
 //      clear tests of up to 64 path nodes one per lane with a ballot for the first failure.  The
 //      leg leaves its piece count and its interior anchors as grid nodes, not doubles.
-//   3. k_rrt_count: the tile again; a trajectory's pieces are summed, the budget decided, the new
+//   3. k_rrt_count: a lane per leg; a trajectory's pieces are summed, the budget decided, the new
 //      segment count and the trajectory's flags written.
-//   4. the scan: the split's three k_scan_* launches (launch_count_scan).
-//   5. k_rrt_write: the tile, a lane per OUTPUT row as in k_sub_write: points from the anchors,
-//      lengths and times, and the copies of everything else.
+//   4. the scan of the new segment counts (launch_count_scan).
+//   5. k_rrt_write: a lane per output row (row_map): points from the anchors, lengths and times,
+//      and the copies of everything else.
 // Every store is guarded by the capacity the header names (min(max_pieces S, 16 B) segments, B
 // more waypoints); only offsets that are not a CSR can reach a guard.  Every window index is
 // below Nw <= 32,768 by construction of the window; the search is not entered above the cap.
@@ -41,72 +41,41 @@
 namespace tgms {
 namespace {
 
-using namespace seg_tile;  // TILE, Tile, load_tile, lane_segment
+using namespace seg_tile;
 
-constexpr int BLOCK = 256;          // threads of the tile kernels
-constexpr int WAVES = BLOCK / W64;  // their wavefronts
 constexpr int LEGS = TGMS_MAX_SEGMENTS;  // record slots per trajectory in the scratch
 constexpr int SEARCH_THREADS = 512;  // eight wavefronts; two such workgroups a CU
 constexpr int SEARCH_BLOCKS = 512;   // the persistent grid: two workgroups for each of 256 CUs
 constexpr int CTL_WORDS = 4;
 constexpr size_t SEARCH_LDS = (size_t)reroute::WINDOW_NODES * sizeof(uint16_t) + CTL_WORDS * sizeof(int);
 
-__device__ __forceinline__ int wave_inclusive(int v, int lane) {
-#pragma unroll
-    for (int o = 1; o < W64; o <<= 1) {
-        const int up = __shfl_up(v, o, W64);
-        v += lane >= o ? up : 0;
-    }
-    return v;
-}
-
-// The sum of v over the lanes sb .. sb + M - 1 of this lane's trajectory.
-__device__ __forceinline__ int trajectory_sum(int v, int sb, int M) {
-    int tot = 0;
-#pragma unroll
-    for (int j = 0; j < TGMS_MAX_SEGMENTS; ++j) {
-        const int x = __shfl(v, std::min(sb + j, W64 - 1), W64);
-        tot += j < M ? x : 0;
-    }
-    return tot;
-}
-
 __global__ __launch_bounds__(BLOCK) void k_rrt_classify(int32_t B, const int32_t* __restrict__ so,
                                                         const double* __restrict__ W, inflate::Grid g,
                                                         const int32_t* __restrict__ table,
                                                         reroute::Record* __restrict__ recs, int32_t* __restrict__ list,
                                                         int32_t* __restrict__ count, int32_t* __restrict__ hops) {
-    const int lane = threadIdx.x & (W64 - 1);
-    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x / W64));
-    const int64_t b0 = ((int64_t)blockIdx.x * WAVES + wave) * TILE;
-    if (b0 >= B) return;  // the whole wavefront
-    const int nb = (int)std::min<int64_t>(TILE, B - b0);
-    Tile x;
-    load_tile(so, b0, nb, x);
-    int tr, sb, M;
-    int64_t gs;
-    lane_segment(x, lane, tr, sb, M, gs);
-    const bool mine = lane < x.base[TILE];
+    Lane l;
+    if (!wave_tile(B, so, l)) return;
     int32_t fl = 0;
-    if (mine) {
-        const double* w = W + (gs + b0 + tr) * 3;  // rows s + b and s + b + 1
+    if (l.mine) {
+        const double* w = W + (l.gs + l.b0 + l.tr) * 3;  // rows s + b and s + b + 1
         const double w0[3] = {w[0], w[1], w[2]}, w1[3] = {w[3], w[4], w[5]};
         int32_t lo[3], hi[3];
         fl = reroute::classify(g, table, w0, w1, lo, hi);
     }
-    const int64_t slot = (b0 + tr) * LEGS + (lane - sb);
-    const bool cand = mine && fl < 0;
-    if (mine) {
+    const int64_t slot = (l.b0 + l.tr) * LEGS + (l.lane - l.sb);
+    const bool cand = l.mine && fl < 0;
+    if (l.mine) {
         recs[slot].head = reroute::pack_head(1, cand ? TGMS_RRT_BLOCKED : fl);
-        if (hops && gs < so[B]) hops[gs] = TGMS_NEAR_NONE;  // offsets that are not a CSR must not reach past S
+        if (hops && l.gs < so[B]) hops[l.gs] = TGMS_NEAR_NONE;  // offsets that are not a CSR must not reach past S
     }
     const unsigned long long m = __ballot(cand);
     if (m != 0ull) {
         const int leader = __ffsll(m) - 1;
         int base = 0;
-        if (lane == leader) base = atomicAdd(count, __popcll(m));
+        if (l.lane == leader) base = atomicAdd(count, __popcll(m));
         base = __shfl(base, leader, W64);
-        if (cand) list[base + __popcll(m & ((1ull << lane) - 1ull))] = (int32_t)slot;
+        if (cand) list[base + __popcll(m & ((1ull << l.lane) - 1ull))] = (int32_t)slot;
     }
 }
 
@@ -250,14 +219,13 @@ struct LegRows {
     int rows, sum;  // rows of this leg; of its trajectory
     bool full;
 };
-__device__ __forceinline__ LegRows leg_rows(const reroute::Record* __restrict__ recs, int64_t slot, bool mine, int sb,
-                                            int M) {
+__device__ __forceinline__ LegRows leg_rows(const reroute::Record* __restrict__ recs, const Lane& l) {
     LegRows r;
-    r.head = mine ? recs[slot].head : 0;
-    const int sum = trajectory_sum(reroute::head_pieces(r.head), sb, M);
+    r.head = l.mine ? recs[(l.b0 + l.tr) * LEGS + (l.lane - l.sb)].head : 0;
+    const int sum = trajectory_sum(reroute::head_pieces(r.head), l.sb, l.M);
     r.full = sum > TGMS_MAX_SEGMENTS;
-    r.rows = mine ? (r.full ? 1 : reroute::head_pieces(r.head)) : 0;
-    r.sum = r.full ? M : sum;
+    r.rows = l.mine ? (r.full ? 1 : reroute::head_pieces(r.head)) : 0;
+    r.sum = r.full ? l.M : sum;
     return r;
 }
 
@@ -265,46 +233,18 @@ __global__ __launch_bounds__(BLOCK) void k_rrt_count(int32_t B, const int32_t* _
                                                      const reroute::Record* __restrict__ recs,
                                                      int32_t* __restrict__ cntS, int64_t* __restrict__ cntF,
                                                      int32_t* __restrict__ flags) {
-    const int lane = threadIdx.x & (W64 - 1);
-    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x / W64));
-    const int64_t b0 = ((int64_t)blockIdx.x * WAVES + wave) * TILE;
-    if (b0 >= B) return;  // the whole wavefront
-    const int nb = (int)std::min<int64_t>(TILE, B - b0);
-    Tile x;
-    load_tile(so, b0, nb, x);
-    int tr, sb, M;
-    int64_t gs;
-    lane_segment(x, lane, tr, sb, M, gs);
-    const bool mine = lane < x.base[TILE];
-    const LegRows r = leg_rows(recs, (b0 + tr) * LEGS + (lane - sb), mine, sb, M);
-    const int32_t fl = mine ? reroute::kept_flag(r.head, r.full) : 0;
-    // the trajectory's flags: the OR over its lanes, bit by bit
-    const unsigned long long span = mine ? ((1ull << M) - 1ull) << sb : 0ull;  // M <= 16
-    constexpr int32_t BITS[8] = {TGMS_RRT_BLOCKED, TGMS_RRT_OUTSIDE, TGMS_FEAS_NONFINITE, TGMS_RRT_WINDOW,
-                                 TGMS_RRT_ENDS,    TGMS_RRT_NOPATH,  TGMS_RRT_LONG,       0};
-    int32_t all = r.full ? TGMS_RRT_FULL : (r.sum > M ? TGMS_RRT_DONE : 0);
-#pragma unroll
-    for (int i = 0; i < 7; ++i) all |= (__ballot((fl & BITS[i]) != 0) & span) != 0ull ? BITS[i] : 0;
-    if (mine && lane == sb) {
-        cntS[b0 + tr] = r.sum;
-        cntF[b0 + tr] = 0;
-        if (flags) flags[b0 + tr] = all;
-    }
-#pragma unroll
-    for (int t = 0; t < TILE; ++t) {
-        if (!(x.oob[t] && lane == t)) continue;  // a bad count: one placeholder segment, nothing read
-        cntS[b0 + t] = 1;
-        cntF[b0 + t] = 0;
-        if (flags) flags[b0 + t] = TGMS_FEAS_NONFINITE;
-    }
+    Lane l;
+    if (!wave_tile(B, so, l)) return;
+    const LegRows r = leg_rows(recs, l);
+    const int32_t fl = l.mine ? reroute::kept_flag(r.head, r.full) : 0;
+    constexpr int32_t BITS[7] = {TGMS_RRT_BLOCKED, TGMS_RRT_OUTSIDE, TGMS_FEAS_NONFINITE, TGMS_RRT_WINDOW,
+                                 TGMS_RRT_ENDS,    TGMS_RRT_NOPATH,  TGMS_RRT_LONG};
+    const int32_t all = (r.full ? TGMS_RRT_FULL : (r.sum > l.M ? TGMS_RRT_DONE : 0)) |
+                        trajectory_flags(fl, l.mine, l.sb, l.M, BITS);
+    store_plan(l, r.sum, all, cntS, cntF, flags);
 }
 
-__global__ void k_rrt_empty(int32_t* __restrict__ so_out, int64_t* __restrict__ totals) {
-    if (threadIdx.x == 0 && blockIdx.x == 0) {
-        so_out[0] = 0;
-        totals[0] = 0;
-    }
-}
+__global__ void k_rrt_empty(int32_t* __restrict__ so_out, int64_t* __restrict__ totals) { empty_batch(so_out, totals); }
 
 __global__ __launch_bounds__(BLOCK) void k_rrt_write(int32_t B, const int32_t* __restrict__ so,
                                                      const double* __restrict__ W, const double* __restrict__ T,
@@ -315,133 +255,54 @@ __global__ __launch_bounds__(BLOCK) void k_rrt_write(int32_t B, const int32_t* _
                                                      double* __restrict__ W_out, double* __restrict__ T_out,
                                                      int32_t* __restrict__ parent, int32_t* __restrict__ seg_flags,
                                                      int64_t* __restrict__ totals) {
-    const int lane = threadIdx.x & (W64 - 1);
-    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x / W64));
     if (blockIdx.x == 0 && threadIdx.x == 0) totals[0] = scan_totals[0];
-    const int64_t b0 = ((int64_t)blockIdx.x * WAVES + wave) * TILE;
-    if (b0 >= B) return;  // the whole wavefront
-    const int nb = (int)std::min<int64_t>(TILE, B - b0);
+    Lane l;
+    if (!wave_tile(B, so, l)) return;
     // the capacities of the caller's buffers (include/tgms.h)
     const int64_t capS = std::min<int64_t>((int64_t)so[B] * max_pieces, (int64_t)TGMS_MAX_SEGMENTS * B), capW = capS + B;
-    const double nan = __builtin_nan("");
-    Tile x;
-    load_tile(so, b0, nb, x);
-    // as a leg: this lane's rows and the rows of the tile's legs up to it
-    int tr, sb, M;
-    int64_t gs;
-    lane_segment(x, lane, tr, sb, M, gs);
-    const LegRows mr = leg_rows(recs, (b0 + tr) * LEGS + (lane - sb), lane < x.base[TILE], sb, M);
-    const int cnt = mr.rows;
-    const int inc = wave_inclusive(cnt, lane);
-    const int total = __shfl(inc, W64 - 1, W64);  // <= 64: TGMS_MAX_SEGMENTS a trajectory
-    // as an output row: the leg whose rows hold row `lane` of the tile is the number of legs whose
-    // inclusive count is at most `lane`
-    int leg = 0;
-#pragma unroll
-    for (int step = W64 / 2; step >= 1; step >>= 1) {
-        const int v = __shfl(inc, leg + step - 1, W64);
-        leg += v <= lane ? step : 0;
-    }
-    const bool live = lane < total;
-    leg = std::min(leg, W64 - 1);
-    const int32_t lhead = __shfl(mr.head, leg, W64);
-    const int lfull = __shfl((int)mr.full, leg, W64);
-    const int lrows = __shfl(cnt, leg, W64);
-    const int piece = lane - __shfl(inc - cnt, leg, W64);  // the row's piece within its leg
-    int ltr, lsb, lM;
-    int64_t lgs;
-    lane_segment(x, leg, ltr, lsb, lM, lgs);
-    // the row's trajectory: its first row in the tile, its rows, its first row afterwards
-    int tbase = 0, tcnt = 0;
-    int64_t so2 = 0;
-#pragma unroll
-    for (int t = 0; t < TILE; ++t) {
-        if (t >= nb) continue;
-        const int32_t so_t = __builtin_amdgcn_readfirstlane(so_out[b0 + t]);
-        const int hi = x.base[t + 1] > 0 ? __shfl(inc, x.base[t + 1] - 1, W64) : 0;
-        const int lo = x.base[t] > 0 ? __shfl(inc, x.base[t] - 1, W64) : 0;
-        tbase = ltr == t ? lo : tbase;
-        tcnt = ltr == t ? hi - lo : tcnt;
-        so2 = ltr == t ? (int64_t)so_t : so2;
-        if (x.oob[t] && lane == 0) {
-            // a segment count outside 1..16: one placeholder segment, a NaN time, two NaN
-            // waypoints; the solve that follows rejects this row alone
-            const int64_t w0 = so_t + b0 + t;
-            if (so_t < capS) {
-                if (T_out) T_out[so_t] = nan;
-                if (parent) parent[so_t] = TGMS_NEAR_NONE;
-                if (seg_flags) seg_flags[so_t] = TGMS_FEAS_NONFINITE;
-            }
-            for (int e = 0; e < 6; ++e)
-                if (w0 + e / 3 < capW) W_out[w0 * 3 + e] = nan;
-        }
-    }
-    if (!live) return;
-    const int64_t b = b0 + ltr;
-    const int q = lane - tbase;  // the row within its trajectory
-    const int64_t orow = so2 + q;
-    const reroute::Record* rec = recs + (b * LEGS + (leg - lsb));
-    const double* w = W + (lgs + b) * 3;  // the leg's rows s + b and s + b + 1
+    // as a leg: this lane's rows; as an output row: piece r.at of leg r.leg
+    const LegRows mr = leg_rows(recs, l);
+    const Row r = row_map(l, mr.rows, so_out);
+    const int32_t lhead = __shfl(mr.head, r.leg, W64);
+    const int lfull = __shfl((int)mr.full, r.leg, W64);
+    const int lrows = __shfl(mr.rows, r.leg, W64);
+    placeholder_rows(l, r, capS, capW, W_out, T_out, parent, seg_flags);
+    if (!r.live) return;
+    const int64_t b = l.b0 + r.ltr;
+    const int q = l.lane - r.tbase, piece = r.at;  // the row within its trajectory, within its leg
+    const int64_t orow = r.so2 + q;
+    const reroute::Record* rec = recs + (b * LEGS + (r.leg - r.lsb));
+    const double* w = W + (r.lgs + b) * 3;  // the leg's rows s + b and s + b + 1
     const double w0[3] = {w[0], w[1], w[2]}, w1[3] = {w[3], w[4], w[5]};
     double a[3] = {w0[0], w0[1], w0[2]}, e[3] = {w1[0], w1[1], w1[2]};
     if (piece > 0) reroute::node_point(g, rec->anchor[piece - 1], a);
     if (piece < lrows - 1) reroute::node_point(g, rec->anchor[piece], e);
-    if (orow + b < capW) {
-        double* o = W_out + (orow + b) * 3;
-#pragma unroll
-        for (int ax = 0; ax < 3; ++ax) o[ax] = a[ax];
-    }
-    if (q == tcnt - 1 && orow + 1 + b < capW) {  // the trajectory's last waypoint
-        double* o = W_out + (orow + 1 + b) * 3;
-#pragma unroll
-        for (int ax = 0; ax < 3; ++ax) o[ax] = w1[ax];
-    }
+    if (orow + b < capW) copy3(W_out + (orow + b) * 3, a);
+    if (q == r.tcnt - 1 && orow + 1 + b < capW) copy3(W_out + (orow + 1 + b) * 3, w1);  // the trajectory's last waypoint
     if (orow < capS) {
         if (T_out) {
-            const double Ts = T[lgs];
+            const double Ts = T[r.lgs];
             T_out[orow] = lrows > 1 ? reroute::piece_time(Ts, reroute::length(a, e), reroute::length(w0, w1)) : Ts;
         }
-        if (parent) parent[orow] = (int32_t)lgs;
+        if (parent) parent[orow] = (int32_t)r.lgs;
         if (seg_flags) seg_flags[orow] = lrows > 1 ? 0 : reroute::kept_flag(lhead, lfull != 0);
     }
 }
 
-struct Scratch {
-    int64_t *cntF, *sumS, *sumF, *totals;
-    int32_t *cntS, *list, *count;
+struct Scratch : ScanScratch {
+    int32_t *cntS, *count, *list;
     reroute::Record* recs;
-    size_t bytes;
+    Scratch(int32_t B, void* base) : ScanScratch(B, base, true) {
+        cntS = take<int32_t>(n);
+        count = take<int32_t>(1);
+        list = take<int32_t>(n * LEGS);
+        recs = take<reroute::Record>(n * LEGS);
+    }
 };
-
-Scratch layout(int32_t B, void* base) {
-    const size_t n = (size_t)std::max(B, 0), nblk = count_scan_blocks(B);
-    auto up = [](size_t v) { return (v + 255) & ~size_t(255); };
-    char* p = static_cast<char*>(base);
-    size_t off = 0;
-    Scratch s;
-    s.cntF = reinterpret_cast<int64_t*>(p + off);
-    off = up(off + n * sizeof(int64_t));
-    s.sumS = reinterpret_cast<int64_t*>(p + off);
-    off = up(off + nblk * sizeof(int64_t));
-    s.sumF = reinterpret_cast<int64_t*>(p + off);
-    off = up(off + nblk * sizeof(int64_t));
-    s.totals = reinterpret_cast<int64_t*>(p + off);
-    off = up(off + 2 * sizeof(int64_t));
-    s.cntS = reinterpret_cast<int32_t*>(p + off);
-    off = up(off + n * sizeof(int32_t));
-    s.count = reinterpret_cast<int32_t*>(p + off);
-    off = up(off + sizeof(int32_t));
-    s.list = reinterpret_cast<int32_t*>(p + off);
-    off = up(off + n * LEGS * sizeof(int32_t));
-    s.recs = reinterpret_cast<reroute::Record*>(p + off);
-    off = up(off + n * LEGS * sizeof(reroute::Record));
-    s.bytes = off;
-    return s;
-}
 
 }  // namespace
 
-size_t reroute_scratch_bytes(int32_t B) { return layout(B, nullptr).bytes; }
+size_t reroute_scratch_bytes(int32_t B) { return Scratch(B, nullptr).off; }
 
 hipError_t reroute_prepare() {
     return hipFuncSetAttribute(reinterpret_cast<const void*>(k_rrt_search), hipFuncAttributeMaxDynamicSharedMemorySize,
@@ -456,10 +317,9 @@ hipError_t launch_reroute(int32_t B, const int32_t* seg_offsets, const double* W
         TGMS_LAUNCH(k_rrt_empty, dim3(1), dim3(W64), 0, stream, so_out, totals);
         return hipSuccess;
     }
-    const Scratch s = layout(B, scratch);
+    const Scratch s(B, scratch);
     const inflate::Grid g = inflate::make_grid(fld);
-    const int64_t tiles = ((int64_t)B + TILE - 1) / TILE;
-    const unsigned blocks = (unsigned)((tiles + WAVES - 1) / WAVES);
+    const unsigned blocks = wave_tile_blocks(B);
     if (const hipError_t e = hipMemsetAsync(s.count, 0, sizeof(int32_t), stream); e != hipSuccess) return e;
     TGMS_LAUNCH(k_rrt_classify, dim3(blocks), dim3(BLOCK), 0, stream, B, seg_offsets, W, g, table, s.recs, s.list, s.count,
                 hops);
