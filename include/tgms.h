@@ -45,7 +45,7 @@
  *     capture with no slab large enough) return TGMS_ERR_UNSUPPORTED while their stream is
  *     capturing.
  *     tgms_extrema_batch_device, tgms_bounds_batch_device, tgms_thrust_batch_device,
- *     tgms_rate_batch_device, tgms_dilate_batch_device and tgms_corridor_batch_device (one kernel, no plan, no scratch) may be captured for any
+ *     tgms_rate_batch_device, tgms_dilate_batch_device, tgms_retime_batch_dev and tgms_corridor_batch_device (one kernel, no plan, no scratch) may be captured for any
  *     batch, ragged included; so may tgms_field_occupancy_device and
  *     tgms_corridor_inflate_batch_device (no plan, no scratch), and tgms_field_edt_device (its
  *     workspace is the caller's);
@@ -120,7 +120,7 @@ tgms_status tgms_create(tgms_handle** out, int device);
 /* The explicit host backend (BASELINE config 1: a ROS 2 node with no GPU; the reference
  * generates on the executor thread's CPU, src/TrajectoryGenerator.cpp:54-57, :71).  A host
  * handle runs tgms_solve_batch (reduced method), tgms_sample_batch, tgms_extrema_batch,
- * tgms_bounds_batch, tgms_thrust_batch, tgms_rate_batch, tgms_dilate_batch, tgms_corridor_batch, tgms_corridor_split_batch, tgms_cut_batch, tgms_separation_batch, tgms_neighbors_batch, tgms_clearance_batch, tgms_field_clearance_batch, tgms_corridor_inflate_batch and tgms_field_edt on the calling thread with the GPU path's conventions; every other entry point returns
+ * tgms_bounds_batch, tgms_thrust_batch, tgms_rate_batch, tgms_dilate_batch, tgms_retime_batch, tgms_corridor_batch, tgms_corridor_split_batch, tgms_cut_batch, tgms_separation_batch, tgms_neighbors_batch, tgms_clearance_batch, tgms_field_clearance_batch, tgms_corridor_inflate_batch and tgms_field_edt on the calling thread with the GPU path's conventions; every other entry point returns
  * TGMS_ERR_UNSUPPORTED on it.  Chosen by the caller only: tgms_create never falls back to
  * it. */
 tgms_status tgms_create_host(tgms_handle** out);
@@ -771,6 +771,73 @@ tgms_status tgms_dilate_batch(tgms_handle* h, int32_t B, const int32_t* seg_offs
                               const double* coeffs, double g, const tgms_limits* limits,
                               const tgms_thrust_limits* tlimits, double s_lo, double s_hi, double* scale,
                               int32_t* active, int32_t* flags, double* seg_times_out, double* coeffs_out);
+
+/* ---- segment re-timing: lengthen only the segments that break a limit ----
+ * The cheaper repair.  tgms_dilate_batch stretches the whole flight by the factor its single worst
+ * instant needs: a ten-segment trajectory whose third leg is too fast gets nine legs slowed that
+ * were fine.  This call re-allocates time per segment instead: every segment gets the factor its
+ * OWN continuous peaks ask for, and the caller solves again with the new times (the coefficients
+ * are not scaled: unequal factors change the optimum), repeats a few rounds and closes whatever
+ * is left with one tgms_dilate_batch.  Only the times feed the next tgms_solve_batch_device;
+ * nothing crosses to the host in between.
+ *   Per segment i with time T_i: v_i, a_i, j_i are the maxima of ||p'||, ||p''||, ||p'''|| over
+ * the closed interval [0, T_i], located as the bounds call locates them and with the square root
+ * of the squared maximum formed as that call forms it; a constant segment gives exactly 0.0.
+ *     r_i = max(v_i / v_max, sqrt(a_i / a_max), cbrt(j_i / j_max))
+ * (an infinite limit contributes 0; this is the dilation's s_kin taken per segment),
+ *     s_i = min(s_hi, max(s_lo, r_i)),      seg_times_out[i] = s_i T_i   (one rounded product).
+ * s_lo < 1 also shortens the segments with slack, s_lo = 1 never shortens; s_hi bounds the growth
+ * of one round.  r_i is the factor that would bring the segment's own peaks to the limits if its
+ * shape stayed the same; the re-solve changes the shape, so r_max after a round is not 1: nothing
+ * is claimed about convergence, the flags of the next call say where it stands.
+ *   seg_rec [S][TGMS_RETIME_STRIDE], in the caller's segment order: v_i a_i j_i r_i.  rec
+ * [B][TGMS_RETIME_REC]: r_max D_in D_out.  r_max is the largest r_i of the trajectory and equals
+ * it to the bit; D_in and D_out are the left-to-right prefix sums of T and of seg_times_out (the
+ * bounds record's duration rule).  flags [B]: TGMS_RT_OVER when r_max > 1, a strict comparison on
+ * the very value stored (the trajectory breaks a limit somewhere); TGMS_RT_CAPPED when some r_i >
+ * s_hi (that segment got less than it asked for); TGMS_RT_CHANGED when some s_i != 1 (the times
+ * differ from the input).  flags >> TGMS_RT_SEG_SHIFT is the local index 0 .. M_b-1 of the
+ * segment that holds r_max, ties to the lowest.
+ *   seg_times_out may be exactly seg_times (in place) or an array that does not overlap it;
+ * partial overlap is undefined.  In place and out of place give the same bits.
+ *   TGMS_ERR_INVALID_ARG: s_lo or s_hi not finite or outside 0 < s_lo <= 1 <= s_hi; v_max, a_max
+ * or j_max NaN or <= 0; all three infinite; limits == NULL (its pmin / pmax are ignored); every
+ * output NULL; an fp64 device array that is not 16-byte aligned.  B == 0 is TGMS_OK and launches
+ * nothing.
+ *   A trajectory with a non-finite coefficient or time, with a T_i that is not > 0, with a
+ * non-finite result or, in the device call, with a segment count outside 1..TGMS_MAX_SEGMENTS
+ * gets TGMS_FEAS_NONFINITE alone, an all-NaN rec row and all-NaN seg_rec rows, and its times are
+ * copied unchanged; for a bad segment count nothing is read or written for its segments.  Its
+ * neighbours are unaffected: no result depends on the other trajectories of the batch.
+ *   Accuracy: v_i, a_i, j_i within 1e-9 relative of the true maxima (the bounds call's contract,
+ * with its caveat: a touch of a derivative without a sign change may be skipped); r_i, s_i T_i
+ * and the record follow from them in a handful of roundings.  Host and device agree to that
+ * accuracy, not to the bit.
+ *   Out of scope: thrust, tilt and body rate.  Gravity does not scale with time, so they have no
+ * per-segment closed form; the caller closes those, and whatever the re-solve leaves over, with
+ * tgms_dilate_batch.
+ *   tgms_retime_batch_dev is one kernel launch with no host plan and no handle scratch, so it
+ * may be captured into a HIP graph for any batch, ragged included.  On a multi handle it runs on
+ * device 0; on a host handle it returns TGMS_ERR_UNSUPPORTED.  tgms_retime_batch on a host
+ * handle computes on the calling thread (the same rule from the same code); on a GPU handle it
+ * does one upload, the launch and one download, like tgms_rate_batch. */
+#define TGMS_RETIME_STRIDE 4 /* seg_rec row: v a j r */
+#define TGMS_RETIME_REC 3    /* rec row: r_max D_in D_out */
+#define TGMS_RT_OVER 1       /* r_max > 1: a limit is exceeded on some segment */
+#define TGMS_RT_CAPPED 2     /* some r_i > s_hi */
+#define TGMS_RT_CHANGED 4    /* some s_i != 1 */
+/* TGMS_FEAS_NONFINITE (16) is reused */
+#define TGMS_RT_SEG_SHIFT 8 /* flags >> 8: the local index of the segment holding r_max */
+tgms_status tgms_retime_batch_dev(tgms_handle* h, int32_t B, const int32_t* d_seg_offsets,
+                                  const double* d_seg_times, const double* d_coeffs,
+                                  const tgms_limits* limits /* host; pmin/pmax ignored */, double s_lo, double s_hi,
+                                  double* d_seg_times_out /* [S], nullable */,
+                                  double* d_seg_rec /* [S][TGMS_RETIME_STRIDE], nullable */,
+                                  double* d_rec /* [B][TGMS_RETIME_REC], nullable */,
+                                  int32_t* d_flags /* [B], nullable */, void* stream);
+tgms_status tgms_retime_batch(tgms_handle* h, int32_t B, const int32_t* seg_offsets, const double* seg_times,
+                              const double* coeffs, const tgms_limits* limits, double s_lo, double s_hi,
+                              double* seg_times_out, double* seg_rec, double* rec, int32_t* flags);
 
 /* ---- corridor containment: worst excursion from per-segment convex polytopes ----
  * Does each segment stay inside its safe flight corridor.  Waypoints come from a path through

@@ -45,6 +45,9 @@ RATE_HIGH = 1  # with FEAS_NONFINITE
 DIL_CAPPED = 1  # tgms_dilate_batch: still infeasible at s_hi; with FEAS_NONFINITE
 DIL_FLAG_MASK, DIL_EVALS_SHIFT = 0xFF, 8  # flags >> 8: evaluations of the thrust record
 DIL_NONE, DIL_SPEED, DIL_ACCEL, DIL_JERK, DIL_THRUST_HIGH, DIL_THRUST_LOW, DIL_TILT = range(7)  # the active limit
+RETIME_STRIDE, RETIME_REC = 4, 3  # tgms_retime_batch: seg_rec row v a j r; rec row r_max D_in D_out
+RT_OVER, RT_CAPPED, RT_CHANGED = 1, 2, 4  # with FEAS_NONFINITE
+RT_SEG_SHIFT = 8  # flags >> 8: the local index of the segment holding r_max
 COR_STRIDE = 2  # m_max t_max
 COR_MAX_FACES = 256  # faces of one segment at most
 COR_OUTSIDE, COR_BAD_FACE = 1, 32  # with FEAS_NONFINITE; indices use NEAR_NONE
@@ -74,6 +77,7 @@ EXPORTS = [
     "tgms_thrust_batch", "tgms_thrust_batch_device",
     "tgms_rate_batch", "tgms_rate_batch_device",
     "tgms_dilate_batch", "tgms_dilate_batch_device",
+    "tgms_retime_batch", "tgms_retime_batch_dev",
     "tgms_corridor_batch", "tgms_corridor_batch_device",
     "tgms_corridor_split_batch", "tgms_corridor_split_batch_device",
     "tgms_cut_batch", "tgms_cut_batch_device",
@@ -283,6 +287,10 @@ def load(path: str = ""):
     L.tgms_dilate_batch.argtypes = [vp, i32, vp, vp, vp, dbl, ctypes.POINTER(Limits), ctypes.POINTER(ThrustLimits),
                                     dbl, dbl, vp, vp, vp, vp, vp]
     L.tgms_dilate_batch.restype = ctypes.c_int
+    L.tgms_retime_batch_dev.argtypes = [vp, i32, vp, vp, vp, ctypes.POINTER(Limits), dbl, dbl, vp, vp, vp, vp, vp]
+    L.tgms_retime_batch_dev.restype = ctypes.c_int
+    L.tgms_retime_batch.argtypes = [vp, i32, vp, vp, vp, ctypes.POINTER(Limits), dbl, dbl, vp, vp, vp, vp]
+    L.tgms_retime_batch.restype = ctypes.c_int
     L.tgms_corridor_batch_device.argtypes = [vp, i32, vp, vp, vp, ctypes.c_int64, vp, vp, dbl, vp, vp, vp, vp, vp, vp]
     L.tgms_corridor_batch_device.restype = ctypes.c_int
     L.tgms_corridor_batch.argtypes = [vp, i32, vp, vp, vp, ctypes.c_int64, vp, vp, dbl, vp, vp, vp, vp, vp]

@@ -26,8 +26,8 @@ ARCH = os.environ.get("TGMS_ARCH", "gfx950")
 HIP_FLAGS = ["--offload-arch=" + ARCH, "-O3", "-std=c++17", "-fPIC", "-I" + INCLUDE, "-I" + CSRC]
 
 HIP_SOURCES = ["tgms_reduced.hip", "tgms_dense.hip", "tgms_band.hip", "tgms_sample.hip", "tgms_extrema.hip",
-               "tgms_bounds.hip", "tgms_thrust.hip", "tgms_rate.hip", "tgms_dilate.hip", "tgms_corridor.hip",
-               "tgms_corridor_split.hip", "tgms_cut.hip", "tgms_separation.hip", "tgms_neighbors.hip",
+               "tgms_bounds.hip", "tgms_thrust.hip", "tgms_rate.hip", "tgms_dilate.hip", "tgms_retime.hip",
+               "tgms_corridor.hip", "tgms_corridor_split.hip", "tgms_cut.hip", "tgms_separation.hip", "tgms_neighbors.hip",
                "tgms_clearance.hip", "tgms_field.hip", "tgms_inflate.hip", "tgms_subdivide.hip", "tgms_reroute.hip",
                "tgms_edt.hip", "tgms_repair.hip", "tgms_capi.hip", "tgms_capi_multi.hip",
                "tgms_capi_analysis.hip", "tgms_capi_map.hip"]

@@ -1,10 +1,11 @@
 // tgms_capi_analysis.hip — the calls on a solved batch (include/tgms.h): extrema, bounds, thrust,
-// rate, dilation, corridor containment and split, replan cut, separation, neighbours, clearance.
-// Each call keeps one sequence: enter, offsets, rules, empty batch, pointers, host backend,
-// stage, launch, download.
+// rate, dilation, re-timing, corridor containment and split, replan cut, separation, neighbours,
+// clearance.  Each call keeps one sequence: enter, offsets, rules, empty batch, pointers, host
+// backend, stage, launch, download.
 #include "tgms_capi.h"
 #include "tgms_dilate_core.h"
 #include "tgms_host.h"
+#include "tgms_retime_core.h"
 #include "tgms_separation_core.h"
 
 #include <algorithm>
@@ -346,6 +347,76 @@ tgms_status tgms_dilate_batch(tgms_handle* h, int32_t B, const int32_t* so, cons
     if (s != TGMS_OK) return s;
     TGMS_HIP(h, tgms::launch_dilate(B, dSo, dT, dC, g, lim, s_lo, s_hi, out.dev(oS), out.dev(oA), out.dev(oF), out.dev(oT),
                                     out.dev(oC), h->stream));
+    return out.download(h);
+}
+
+// ---- segment re-timing: lengthen only the segments that break a limit ----
+
+// The argument rules the two re-timing entry points share (include/tgms.h), and the three limits
+// a launch carries (+inf: unchecked).
+static tgms_status check_retime(tgms_handle* h, int32_t B, const tgms_limits* limits, double s_lo, double s_hi,
+                                bool any_output, tgms::retime::Lim* out) {
+    if (B < 0) return set_err(h, TGMS_ERR_INVALID_ARG, "bad B");
+    if (!(s_lo > 0.0) || !(s_lo <= 1.0) || !(s_hi >= 1.0) || !std::isfinite(s_hi))
+        return set_err(h, TGMS_ERR_INVALID_ARG, "the scale interval needs 0 < s_lo <= 1 <= s_hi, both finite");
+    if (!limits) return set_err(h, TGMS_ERR_INVALID_ARG, "limits is NULL");
+    *out = tgms::retime::Lim{limits->v_max, limits->a_max, limits->j_max};
+    if (!(out->v_max > 0.0) || !(out->a_max > 0.0) || !(out->j_max > 0.0))  // NaN fails too
+        return set_err(h, TGMS_ERR_INVALID_ARG, "v_max, a_max and j_max must be > 0");
+    if (std::isinf(out->v_max) && std::isinf(out->a_max) && std::isinf(out->j_max))
+        return set_err(h, TGMS_ERR_INVALID_ARG, "all three limits are infinite");
+    if (!any_output) return set_err(h, TGMS_ERR_INVALID_ARG, "every output is NULL");
+    return TGMS_OK;
+}
+
+tgms_status tgms_retime_batch_dev(tgms_handle* h, int32_t B, const int32_t* d_so, const double* dT, const double* dC,
+                                  const tgms_limits* limits, double s_lo, double s_hi, double* dT_out,
+                                  double* d_seg_rec, double* d_rec, int32_t* d_flags, void* stream) {
+    if (tgms_status e = enter(h, __func__); e != TGMS_OK) return e;
+    tgms::retime::Lim lim;
+    const tgms_status s = check_retime(h, B, limits, s_lo, s_hi, dT_out || d_seg_rec || d_rec || d_flags, &lim);
+    if (s != TGMS_OK) return s;
+    if (B == 0) return TGMS_OK;
+    if (!d_so || !dT || !dC) return set_err(h, TGMS_ERR_INVALID_ARG, "NULL device pointer");
+    TGMS_CHECK_ALIGNED(h, dT, dC, dT_out, d_seg_rec, d_rec);
+    TGMS_HIP(h, tgms::launch_retime(B, d_so, dT, dC, lim, s_lo, s_hi, dT_out, d_seg_rec, d_rec, d_flags,
+                                    static_cast<hipStream_t>(stream)));
+    return TGMS_OK;
+}
+
+tgms_status tgms_retime_batch(tgms_handle* h, int32_t B, const int32_t* so, const double* seg_times,
+                              const double* coeffs, const tgms_limits* limits, double s_lo, double s_hi,
+                              double* seg_times_out, double* seg_rec, double* rec, int32_t* flags) {
+    if (tgms_status e = enter(h); e != TGMS_OK) return e;
+    tgms_status s = check_offsets(h, B, so, TGMS_MAX_SEGMENTS, nullptr, nullptr);
+    if (s != TGMS_OK) return s;
+    tgms::retime::Lim lim;
+    s = check_retime(h, B, limits, s_lo, s_hi, seg_times_out || seg_rec || rec || flags, &lim);
+    if (s != TGMS_OK) return s;
+    if (B == 0) return TGMS_OK;
+    if (!seg_times || !coeffs) return set_err(h, TGMS_ERR_INVALID_ARG, "NULL pointer");
+    if (h->host) {
+        for (int32_t b = 0; b < B; ++b) {
+            const int64_t s0 = so[b];
+            const int fl = tgms::host::retime(so[b + 1] - so[b], coeffs + s0 * 24, seg_times + s0, lim, s_lo, s_hi,
+                                              seg_times_out ? seg_times_out + s0 : nullptr,
+                                              seg_rec ? seg_rec + s0 * TGMS_RETIME_STRIDE : nullptr,
+                                              rec ? rec + (int64_t)b * TGMS_RETIME_REC : nullptr);
+            if (flags) flags[b] = fl;
+        }
+        return TGMS_OK;
+    }
+    const size_t S = (size_t)so[B], n = (size_t)B;
+    Outputs out;
+    const auto oSeg = out.add(seg_rec, S * TGMS_RETIME_STRIDE), oT = out.add(seg_times_out, S);
+    const auto oRec = out.add(rec, n * TGMS_RETIME_REC);
+    const auto oF = out.add(flags, n);
+    double *dT, *dC;
+    int32_t* dSo;
+    s = stage(h, {input(&dT, seg_times, S), input(&dC, coeffs, S * 24), input(&dSo, so, n + 1), output(&out)});
+    if (s != TGMS_OK) return s;
+    TGMS_HIP(h, tgms::launch_retime(B, dSo, dT, dC, lim, s_lo, s_hi, out.dev(oT), out.dev(oSeg), out.dev(oRec),
+                                    out.dev(oF), h->stream));
     return out.download(h);
 }
 

@@ -37,6 +37,7 @@
 #include "tgms_neighbors_core.h"
 #include "tgms_separation_core.h"
 #include "tgms_repair_core.h"
+#include "tgms_retime_core.h"
 #include "tgms_reroute_core.h"
 #include "tgms_subdivide_core.h"
 #include "tgms_rate_core.h"
@@ -448,6 +449,40 @@ int dilate(int M, const double* C, const double* T, double g, const tgms::dilate
     if (scale) *scale = q.s;
     if (active) *active = q.active;
     return q.flags;
+}
+
+int retime(int M, const double* C, const double* T, const tgms::retime::Lim& lim, double s_lo, double s_hi,
+           double* T_out, double* seg_rec, double* rec) {
+    namespace rt = tgms::retime;
+    double chk = 0.0;
+    bool bad = false;
+    for (int i = 0; i < M; ++i) {
+        chk += T[i] * 0.0;
+        bad = bad || !(T[i] > 0.0);
+    }
+    for (int q = 0; q < M * 24; ++q) chk += C[q] * 0.0;
+    bad = bad || !finite(chk);
+    const double inf = HUGE_VAL;
+    const bool run[3] = {seg_rec || lim.v_max < inf, seg_rec || lim.a_max < inf, seg_rec || lim.j_max < inf};
+    rt::Seg g[TGMS_MAX_SEGMENTS];
+    rt::Fold f = rt::fold_init();
+    for (int i = 0; !bad && i < M; ++i) {  // the kernel's phases, unchecked ones skipped when no row is asked for
+        const double* c = C + i * 24;
+        const double n2[3] = {run[0] ? tgms::bounds::norm_item<1>(c, T[i]) : 0.0,
+                              run[1] ? tgms::bounds::norm_item<2>(c, T[i]) : 0.0,
+                              run[2] ? tgms::bounds::norm_item<3>(c, T[i]) : 0.0};
+        g[i] = rt::segment(n2, T[i], lim, s_lo, s_hi);
+        rt::fold(f, i, g[i].row[3], g[i].s, T[i], g[i].T_out);
+    }
+    double r[TGMS_RETIME_REC];
+    const int fl = rt::finish(f, bad, s_hi, r);
+    const bool nan = (fl & TGMS_FEAS_NONFINITE) != 0;
+    for (int q = 0; rec && q < TGMS_RETIME_REC; ++q) rec[q] = r[q];
+    for (int i = 0; i < M; ++i) {  // T_out may be T: every product was formed above
+        for (int q = 0; seg_rec && q < TGMS_RETIME_STRIDE; ++q) seg_rec[i * TGMS_RETIME_STRIDE + q] = nan ? NAN : g[i].row[q];
+        if (T_out) T_out[i] = nan ? T[i] : g[i].T_out;
+    }
+    return fl;
 }
 
 int separation(int Mi, const double* ci, const double* Ti, double t0i, int Mj, const double* cj, const double* Tj,

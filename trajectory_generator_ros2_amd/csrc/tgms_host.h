@@ -10,6 +10,9 @@ namespace tgms {
 namespace dilate {
 struct Lim;
 }
+namespace retime {
+struct Lim;
+}
 namespace host {
 
 // One trajectory (include/tgms.h layouts): waypoints [M+1][3], seg_times [M], end_derivs
@@ -56,6 +59,14 @@ int rate(int M, const double* coeffs, const double* seg_times, double g, double 
 // algorithm is the kernel's (tgms_dilate_core.h), one segment and one evaluation after the other.
 int dilate(int M, const double* coeffs, const double* seg_times, double g, const tgms::dilate::Lim& lim, double s_lo,
            double s_hi, double* scale, int* active, double* T_out, double* C_out);
+
+// Segment re-timing (include/tgms.h tgms_retime_batch) of one trajectory (1 <= M <=
+// TGMS_MAX_SEGMENTS): the times s_i T_i into T_out [M] (may be seg_times), the rows v a j r into
+// seg_rec [M][TGMS_RETIME_STRIDE], r_max D_in D_out into rec [TGMS_RETIME_REC] (each nullable);
+// returns the flags.  The rule and the fold are the kernel's (tgms_retime_core.h), one segment
+// after the other.
+int retime(int M, const double* coeffs, const double* seg_times, const tgms::retime::Lim& lim, double s_lo,
+           double s_hi, double* T_out, double* seg_rec, double* rec);
 
 // Closest approach of one pair (include/tgms.h tgms_separation_batch): trajectory i has Mi
 // segments (coeffs ci, times Ti) and starts at t0i, likewise j.  Mi or Mj == 0 says that the

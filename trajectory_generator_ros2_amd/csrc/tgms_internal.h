@@ -162,6 +162,17 @@ hipError_t launch_dilate(int32_t B, const int32_t* seg_offsets, const double* T,
                          const dilate::Lim& lim, double s_lo, double s_hi, double* scale, int32_t* active,
                          int32_t* flags, double* T_out, double* C_out, hipStream_t stream);
 
+// Segment re-timing (tgms_retime.hip): per segment v a j r into seg_rec [S][TGMS_RETIME_STRIDE] and
+// the time s T into T_out [S] (may be T), per trajectory r_max D_in D_out into rec
+// [B][TGMS_RETIME_REC] and flags [B] (each nullable) against lim (tgms_retime_core.h: each limit
+// > 0, +inf unchecked); the tile of launch_bounds, one launch.
+namespace retime {
+struct Lim;
+}
+hipError_t launch_retime(int32_t B, const int32_t* seg_offsets, const double* T, const double* C,
+                         const retime::Lim& lim, double s_lo, double s_hi, double* T_out, double* seg_rec, double* rec,
+                         int32_t* flags, hipStream_t stream);
+
 // Corridor containment (tgms_corridor.hip): per trajectory m_max t_max into rec
 // [B][TGMS_COR_STRIDE], its segment and face into where [B][2], per segment m_s t_s into
 // seg_rec [S][TGMS_COR_STRIDE] and its face into seg_face [S], flags [B] (each nullable);

@@ -214,6 +214,46 @@ class Solver:
             _ptr(flags), _ptr(T_out), _ptr(C_out)))
         return scale, active, flags, T_out, C_out
 
+    def retime(self, seg_offsets, seg_times, coeffs, limits: _lib.Limits, s_lo: float = 1.0, s_hi: float = 100.0):
+        """Segment re-timing (include/tgms.h tgms_retime_batch): per segment the factor r_i its own
+        continuous peaks ask for against v_max / a_max / j_max of `limits` and the time s_i T_i
+        with s_i = min(s_hi, max(s_lo, r_i)).  Returns (T_out [S], seg_rec [S,4] = v a j r, rec
+        [B,3] = r_max D_in D_out, flags [B] of RT_* bits with the worst segment's index above
+        RT_SEG_SHIFT).  The coefficients are not scaled: solve again with T_out."""
+        so, _, T, C, _ = _csr(seg_offsets, seg_times=seg_times, coeffs=coeffs)
+        B = so.shape[0] - 1
+        T_out = np.zeros_like(T)
+        seg_rec = np.zeros((T.shape[0], _lib.RETIME_STRIDE), dtype=np.float64)
+        rec = np.zeros((B, _lib.RETIME_REC), dtype=np.float64)
+        flags = np.zeros(B, dtype=np.int32)
+        self._check(self._L.tgms_retime_batch(
+            self._h, B, _ptr(so), _ptr(T), _ptr(C), None if limits is None else ctypes.byref(limits), float(s_lo),
+            float(s_hi), _ptr(T_out), _ptr(seg_rec), _ptr(rec), _ptr(flags)))
+        return T_out, seg_rec, rec, flags
+
+    def retime_loop(self, seg_offsets, waypoints, seg_times, limits: _lib.Limits, rounds: int, s_lo: float = 1.0,
+                    s_hi: float = 4.0, end_derivs=None, dilate: bool = True):
+        """Solve, re-time, solve again: up to `rounds` rounds of solve + retime on host arrays,
+        stopping early when no trajectory carries RT_OVER, then a final solve and, if `dilate`, one
+        uniform dilation with the same limits that closes what the rounds left over.  Returns (T,
+        coeffs, history); history holds per round {"over": the share of trajectories with RT_OVER
+        in the round's solve, "mean_D_out": the mean duration the round leaves}.  The round that
+        finds none over is recorded, keeps its times and ends the loop."""
+        so, W, T, _, ED = _csr(seg_offsets, waypoints, seg_times, end_derivs=end_derivs)
+        history = []
+        for _ in range(int(rounds)):
+            C, _, _ = self.solve(so, W, T, ED)
+            T_new, _, rec, flags = self.retime(so, T, C, limits, s_lo, s_hi)
+            over = (flags & _lib.RT_OVER) != 0
+            history.append({"over": float(over.mean()), "mean_D_out": float(np.nanmean(rec[:, 2 if over.any() else 1]))})
+            if not over.any():
+                break
+            T = T_new
+        C, _, _ = self.solve(so, W, T, ED)
+        if dilate:
+            _, _, _, T, C = self.dilate(so, T, C, limits=limits)
+        return T, C, history
+
     def corridor(self, seg_offsets, seg_times, coeffs, faces, face_offsets=None, r: float = 0.0):
         """Corridor containment (include/tgms.h tgms_corridor_batch): faces [F,4] = n[3] d, a point
         inside when n . p <= d; face_offsets [S+1] int64 gives each segment its faces, None
@@ -678,6 +718,17 @@ class Solver:
             None if limits is None else ctypes.byref(limits), None if tlimits is None else ctypes.byref(tlimits),
             float(s_lo), float(s_hi), _ptr(d_scale), _ptr(d_active), _ptr(d_flags), _ptr(d_seg_times_out),
             _ptr(d_coeffs_out), ctypes.c_void_p(stream)))
+
+    def retime_device(self, B: int, d_seg_offsets, d_seg_times, d_coeffs, limits: _lib.Limits, s_lo: float = 1.0,
+                      s_hi: float = 100.0, d_seg_times_out=None, d_seg_rec=None, d_rec=None, d_flags=None,
+                      stream: int = 0) -> None:
+        """tgms_retime_batch_dev: d_seg_times_out [S] fp64 (may be d_seg_times itself), d_seg_rec
+        [S,4] fp64, d_rec [B,3] fp64, d_flags [B] int32 (at least one); the limits are read now,
+        so they may change before the kernel runs."""
+        self._check(self._L.tgms_retime_batch_dev(
+            self._h, int(B), _ptr(d_seg_offsets), _ptr(d_seg_times), _ptr(d_coeffs),
+            None if limits is None else ctypes.byref(limits), float(s_lo), float(s_hi), _ptr(d_seg_times_out),
+            _ptr(d_seg_rec), _ptr(d_rec), _ptr(d_flags), ctypes.c_void_p(stream)))
 
     def corridor_device(self, B: int, d_seg_offsets, d_seg_times, d_coeffs, F: int, d_faces, d_face_offsets=None,
                         r: float = 0.0, d_rec=None, d_where=None, d_seg_rec=None, d_seg_face=None, d_flags=None,
